@@ -3,6 +3,13 @@
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: one rank per GPU under torch.distributed.run — by the caller, or by
                                                           bench.py itself when WORLD_SIZE is not set)
+    python bench.py ... --full                           everything below as well (roofline, CPU baseline, configurations, ...)
+    python bench.py ... --dump-outputs DIR               the last timed step's proof as DIR/proof_bytes.npy (float32, one per byte)
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, `prove_ms`, `phases_ms` and the
+config record come from the timed steps alone.  Everything else this file describes (the Python-mirror cross-check and verification
+of the timed proof, `roofline`, `cpu_baseline`, `configs`, `phases_readme`, `pipelined`, and at N > 1 the `one_proof` leg) runs
+only under --full.
 
 One "step" = one complete prove() of the workload (default: BASELINE configs[4] = MiMC-128, 2^20 trace steps,
 extensionFactor 16, exeQueryCount 48, friQueryCount 64, blake2s256): execution trace, iNTT, LDE, leaf hashing,
@@ -234,6 +241,23 @@ def second_roof(n, transform_ms, npass, traffic_detail=None):
     return out
 
 
+def dump_outputs(out_dir, data, rank, world, limit=64 << 20):
+    """what the timed path returned in its last step, the serialized proof, as float32 (one value per byte, exact): rank 0 writes
+    out_dir/proof_bytes.npy, rank r > 0 out_dir/proof_bytes_rank<r>.npy.  A proof larger than this rank's share of `limit` bytes of
+    .npy data is written as a fixed, seeded sample of its byte positions (proof_bytes_index.npy beside it, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = '' if rank == 0 else f'_rank{rank}'
+    vals = np.frombuffer(data, dtype=np.uint8).astype(np.float32)
+    share = limit // max(world, 1)
+    if vals.size * 4 > share:
+        cap = share // 12                                # float32 value + float64 index per sampled byte
+        pos = np.sort(np.random.default_rng(0x5eed).choice(vals.size, size=cap, replace=False))
+        vals = vals[pos]
+        np.save(os.path.join(out_dir, f'proof_bytes_index{suffix}.npy'), pos.astype(np.float64))
+    np.save(os.path.join(out_dir, f'proof_bytes{suffix}.npy'), vals)
+
+
 def pmc_traffic(logn):
     import subprocess
     try:
@@ -429,7 +453,16 @@ def main():
     ap.add_argument('--test-double-lib', default=None, help=argparse.SUPPRESS)
     # test-only: run the N > 1 flow (process group, one-proof leg over the RCCL communicator) with ONE rank — what a one-GPU box can execute of it
     ap.add_argument('--force-dist', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure as well: Python-mirror cross-check and verification, roofline, CPU baseline, '
+                         'per-configuration children, phase log, pipelined lanes, and (N > 1) the one-proof leg.  Without it a run sets up, '
+                         'warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (the serialized proof, one float32 per byte) '
+                         'as DIR/proof_bytes.npy (rank r > 0: DIR/proof_bytes_rank<r>.npy)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     cpu_mode = args.test_double_lib is not None
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher — one rank per GPU under torch.distributed.run on a free
@@ -536,24 +569,28 @@ def main():
     assert all(st['ntt_points'] == points for st in launched)
     if args.log_trace >= 8:
         assert points == expected_ntt_points(steps, ef), (points, expected_ntt_points(steps, ef))
-    proof = stark.parse(data)
-    # the Python mirror on the same statement: same bytes, its own wall-clock (not part of `value`)
-    mirror_ms = []
-    for _ in range(3):
-        ts = time.perf_counter()
-        mirror_proof = stark.prove(a, [], [seed])
-        mirror_ms.append(round((time.perf_counter() - ts) * 1e3, 3))
-    assert stark.serialize(mirror_proof) == data, 'native driver and Python mirror disagree'
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, data, rank, world)
+    mirror_ms = None
+    if args.full:
+        proof = stark.parse(data)
+        # the Python mirror on the same statement: same bytes, its own wall-clock (not part of `value`)
+        mirror_ms = []
+        for _ in range(3):
+            ts = time.perf_counter()
+            mirror_proof = stark.prove(a, [], [seed])
+            mirror_ms.append(round((time.perf_counter() - ts) * 1e3, 3))
+        assert stark.serialize(mirror_proof) == data, 'native driver and Python mirror disagree'
 
-    # outside the timed region: the proof is valid and the wire format is consistent (reference acceptance criterion)
-    assert len(data) == stark.sizeOf(proof)
-    if rank == 0 or cpu_mode:
-        assert stark.verify(a, stark.parse(data))
-    if dist is not None:
-        # every rank proved its OWN trace: the evaluation roots must all differ (no rank idled or duplicated work)
-        roots = [None] * world
-        dist.all_gather_object(roots, proof['evRoot'].hex())
-        assert len(set(roots)) == world, 'ranks produced identical proofs'
+        # outside the timed region: the proof is valid and the wire format is consistent (reference acceptance criterion)
+        assert len(data) == stark.sizeOf(proof)
+        if rank == 0 or cpu_mode:
+            assert stark.verify(a, stark.parse(data))
+        if dist is not None:
+            # every rank proved its OWN trace: the evaluation roots must all differ (no rank idled or duplicated work)
+            roots = [None] * world
+            dist.all_gather_object(roots, proof['evRoot'].hex())
+            assert len(set(roots)) == world, 'ranks produced identical proofs'
 
     out = None
     if rank == 0 and cpu_mode:
@@ -566,117 +603,6 @@ def main():
         # boundaries; it adds no device synchronisation, so a phase lasts until its last blocking call returned)
         phases = launched[-1]['phases_ms']
         driver_total_ms = launched[-1]['total_ms']
-
-        # ---- roofline of the dominant kernel: one radix-256 NTT pass over n = T*E points
-        import ctypes as C
-        f = stark.air.field
-        w = f.getRootOfUnity(n)
-        src = f.getPowerSeries(0x123456789abcdef0123456789, n)
-        dst = f.newVector(n)
-        wb = w.to_bytes(16, 'little')
-        call = lambda: backend.call('gs_eval_polys_at_roots', C.c_void_p(src.ptr), 1, n, wb, n, C.c_void_p(dst.ptr))
-        call()
-        torch.cuda.synchronize()
-        reps = 20
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(reps):
-            call()
-        e1.record(stream)
-        e1.synchronize()
-        logn = n.bit_length() - 1
-        npass = (logn + 7) // 8
-        transform_ms = e0.elapsed_time(e1) / reps
-        launch_ms = transform_ms / npass
-        # algorithmic bytes: 32 B per element per transform -> one pass launch does 1/npass of a transform
-        alg_bytes_per_launch = 32.0 * n / npass
-        achieved = alg_bytes_per_launch / (launch_ms * 1e-3) / 1e9
-        # counter passes and the CPU baseline run on rank 0 at N = 1 only: at N > 1 the other ranks are waiting at the one-proof leg below
-        traffic, traffic_detail = (None, {'skipped': True}) if (args.no_pmc or world > 1) else pmc_traffic(logn)
-        roofline = {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                    'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
-                    'traffic_source': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child processes of this run (tools/pmc_traffic.py)',
-                    'traffic_detail': traffic_detail,
-                    'kernel': f'k_ntt_wave<4, *> (radix-256 Stockham pass, one wave per tile, lazy five-limb butterflies), {npass} launches per 2^{logn}-point transform',
-                    'launch_ms': round(launch_ms, 4), 'transform_ms': round(transform_ms, 4),
-                    'ntt_kernel_elements_per_sec': round(n / (transform_ms * 1e-3), 1),
-                    'second_roof': second_roof(n, transform_ms, npass, traffic_detail)}
-        del src, dst
-
-        def gpu_digest(log_steps, ef_, exe, fri_, _cache={}):
-            key = (log_steps, ef_, exe, fri_)
-            if key not in _cache:
-                import hashlib
-                if key == (args.log_trace, ef, 48, fri) and seed == 3:
-                    blob = data                                    # the timed proof itself
-                else:
-                    st_ = ga.instantiateMimc(1 << log_steps, {'hashAlgorithm': 'blake2s256', 'extensionFactor': ef_, 'exeQueryCount': exe, 'friQueryCount': fri_}, backend=backend)
-                    blob = Prover(st_.air, {'hashAlgorithm': 'blake2s256', 'extensionFactor': ef_, 'exeQueryCount': exe, 'friQueryCount': fri_}).prove_bytes(
-                        assertions_for(st_, 1 << log_steps, 3), [], [3])
-                _cache[key] = hashlib.sha256(blob).hexdigest()
-            return _cache[key]
-
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(ga, ef, fri, gpu_digest)
-
-        # ---- every BASELINE.json configuration through the product entry (compiled programs, packed seeds), driver-run: wall-clock per
-        # proof, device-busy time and launches per proof (rocprofv3 --kernel-trace of a second child), the reference's own phase log
-        # with device-synchronised times.  Child processes of this run (tools/config_runs.py); N = 1 only
-        configs = None
-        if not args.no_configs and world == 1:
-            import subprocess
-            try:
-                r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'config_runs.py')], capture_output=True, text=True, timeout=600)
-                configs = json.loads([l for l in r.stdout.splitlines() if l.startswith('[')][-1])
-            except Exception as e:   # noqa: BLE001
-                configs = [{'error': repr(e)[:300]}]
-        # the kernel that dominates the PROOF (the NTT pass above dominates the transform metric, not the proof): from the C5 run
-        c5 = next((c for c in (configs or []) if c.get('name') == 'C5' and c.get('dominant_kernel')), None)
-        if c5 is not None:
-            ms_k = c5['dominant_kernel_ms_per_proof']
-            fused_leaves = 'k_merkle_fused<1, 1>' in c5['dominant_kernel']
-            comp = n * 1.875 if fused_leaves else None        # 2^24 leaf hashes + the three node layers above them in the same launch
-            roofline['proof_dominant_kernel'] = {
-                'kernel': c5['dominant_kernel'], 'ms_per_proof': ms_k, 'share_of_device_busy_time': c5['dominant_share'],
-                'device_busy_ms_per_proof': c5['device_busy_ms'],
-                'what': 'evaluation-tree commitment: mergeVectorRows + the first three node layers in one launch (lib/Stark.ts:113-118)' if fused_leaves else None,
-                'bound': 'blake2s compression issue rate (39.5 G compressions/s chip-wide, tools/microbench_hash.hip), not HBM',
-                'compressions_per_sec': None if comp is None else round(comp / (ms_k * 1e-3), 1),
-                'frac_of_compression_roof': None if comp is None else round(comp / (ms_k * 1e-3) / 39.5e9, 4),
-                'algorithmic_GBs': None if comp is None else round(n * (16 + 32 + 28) / (ms_k * 1e-3) / 1e9, 1),
-                'frac_of_hbm_peak': None if comp is None else round(n * (16 + 32 + 28) / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-        # every kernel of the headline proof and of the long Poseidon proof against its roof (tools/config_runs.py: kernel_table): the
-        # kernel trace of the configuration's own child run joined with the library's tally of what each launch had to move
-        roofline['kernels'] = {c_['name']: c_.pop('kernels') for c_ in (configs or []) if c_.get('name') in ('C5', 'C4_long') and c_.get('kernels')}
-        roofline['kernels_note'] = ('per proof: calls and ms from rocprofv3 --kernel-trace of the configuration\'s child run; algorithmic_MB = the bytes the launches HAD to '
-                                    'read once and write once (gs_traffic_enable: tallied by the library per launch from its arguments — an NTT pass 16 B in + 16 B out '
-                                    'per element, a Merkle layer 64 B in + 32 B out per node, ...); frac_hbm against 8 TB/s; frac_own_roof where the kernel\'s own roof '
-                                    'is known (BLAKE2s compression issue 39.5 G/s; NTT passes: issue time of their static VALU mix)')
-        for c_ in (configs or []):
-            c_.pop('kernels', None)
-        # the reference's phase vocabulary for the headline proof (README.md:62-73; lib/Stark.ts:92-152), device-synchronised
-        prover.sync_phases(True)
-        prover.prove_bytes(a, [], [seed])
-        phases_readme = prover.last_stats().get('phases_readme')
-        prover.sync_phases(False)
-
-        # ---- extra leg (reported beside `value`, never as `value`): throughput of a proving service that keeps several
-        # independent proofs in flight on this GPU (genstark_amd/pipeline.py); every proof runs the unmodified prove()
-        pipelined = None
-        if args.lanes > 0 and world == 1:
-            from genstark_amd.pipeline import ProverPool
-            job = (a, [], [seed])
-            with ProverPool(lambda be: ga.mimcProver(steps, {'hashAlgorithm': 'blake2s256', 'extensionFactor': ef, 'exeQueryCount': 48, 'friQueryCount': fri}, backend=be), lanes=args.lanes,
-                            backend_factory=lambda: Backend(device=device_index), native=True) as pool:
-                for _ in range(max(args.warmup, 1)):
-                    pool.on_every_lane(lambda s: s.prove_bytes(*job))
-                tp = time.perf_counter()
-                proofs = pool.prove_many_bytes([job] * args.lane_proofs)
-                dt = time.perf_counter() - tp
-                assert all(pr == data for pr in proofs)                        # same statement -> same bytes as the timed steps
-            pipelined = {'lanes': args.lanes, 'proofs': args.lane_proofs, 'ms_per_proof': round(dt / args.lane_proofs * 1e3, 3),
-                         'value': points * args.lane_proofs / dt, 'unit': 'elements/s',
-                         'note': 'independent proofs in flight on one GPU (one library context + HIP stream per lane): a lane\'s '
-                                 'host-side trace recurrence overlaps the other lanes\' kernels; latency of one proof is prove_ms'}
         out = {
             'metric': 'prove() ms + NTT GF(p) elements/sec, MiMC-128 2^20 steps', 'value': points * world / (ms_per_step * 1e-3),
             'unit': 'elements/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
@@ -689,14 +615,125 @@ def main():
                        'secret_registers': 0, 'field': 'GF(2^128-9*2^32+1): 4x u32 limbs in memory, 5x 26-bit limbs inside the NTT networks',
                        'evaluation_domain': n, 'ntt_points_per_prove': points, 'ntt_transforms_per_prove': launched[-1]['ntt_transforms'],
                        'ntt_points_source': 'gs_prover_last_stats: rows * n of every transform the timed driver launched', 'proof_bytes': len(data)},
-            'prove_ms': ms_per_step, 'per_step_ms': step_ms, 'python_mirror_prove_ms': mirror_ms, 'phases_ms': phases, 'phases_source': 'native driver clock, last timed step', 'driver_total_ms': driver_total_ms, 'roofline': roofline, 'cpu_baseline': cpu,
-            'pipelined': pipelined,
-            'phases_readme': {'ms': phases_readme, 'total_ms': None if not phases_readme else round(sum(m for _, m in phases_readme), 4),
-                              'note': 'the reference\'s own log points (README.md:62-73, lib/Stark.ts:92-152) on ONE extra proof of the headline statement '
-                                      'with the device synchronised at each of them (gs_prover_sync_phases): each entry is that phase alone; the timed '
-                                      'proofs above run asynchronously and overlap them (phases_ms)'},
-            'configs': configs,
+            'prove_ms': ms_per_step, 'per_step_ms': step_ms, 'phases_ms': phases, 'phases_source': 'native driver clock, last timed step', 'driver_total_ms': driver_total_ms,
         }
+        if args.full:
+            # ---- roofline of the dominant kernel: one radix-256 NTT pass over n = T*E points
+            import ctypes as C
+            f = stark.air.field
+            w = f.getRootOfUnity(n)
+            src = f.getPowerSeries(0x123456789abcdef0123456789, n)
+            dst = f.newVector(n)
+            wb = w.to_bytes(16, 'little')
+            call = lambda: backend.call('gs_eval_polys_at_roots', C.c_void_p(src.ptr), 1, n, wb, n, C.c_void_p(dst.ptr))
+            call()
+            torch.cuda.synchronize()
+            reps = 20
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(reps):
+                call()
+            e1.record(stream)
+            e1.synchronize()
+            logn = n.bit_length() - 1
+            npass = (logn + 7) // 8
+            transform_ms = e0.elapsed_time(e1) / reps
+            launch_ms = transform_ms / npass
+            # algorithmic bytes: 32 B per element per transform -> one pass launch does 1/npass of a transform
+            alg_bytes_per_launch = 32.0 * n / npass
+            achieved = alg_bytes_per_launch / (launch_ms * 1e-3) / 1e9
+            # counter passes and the CPU baseline run on rank 0 at N = 1 only: at N > 1 the other ranks are waiting at the one-proof leg below
+            traffic, traffic_detail = (None, {'skipped': True}) if (args.no_pmc or world > 1) else pmc_traffic(logn)
+            roofline = {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                        'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
+                        'traffic_source': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child processes of this run (tools/pmc_traffic.py)',
+                        'traffic_detail': traffic_detail,
+                        'kernel': f'k_ntt_wave<4, *> (radix-256 Stockham pass, one wave per tile, lazy five-limb butterflies), {npass} launches per 2^{logn}-point transform',
+                        'launch_ms': round(launch_ms, 4), 'transform_ms': round(transform_ms, 4),
+                        'ntt_kernel_elements_per_sec': round(n / (transform_ms * 1e-3), 1),
+                        'second_roof': second_roof(n, transform_ms, npass, traffic_detail)}
+            del src, dst
+
+            def gpu_digest(log_steps, ef_, exe, fri_, _cache={}):
+                key = (log_steps, ef_, exe, fri_)
+                if key not in _cache:
+                    import hashlib
+                    if key == (args.log_trace, ef, 48, fri) and seed == 3:
+                        blob = data                                    # the timed proof itself
+                    else:
+                        st_ = ga.instantiateMimc(1 << log_steps, {'hashAlgorithm': 'blake2s256', 'extensionFactor': ef_, 'exeQueryCount': exe, 'friQueryCount': fri_}, backend=backend)
+                        blob = Prover(st_.air, {'hashAlgorithm': 'blake2s256', 'extensionFactor': ef_, 'exeQueryCount': exe, 'friQueryCount': fri_}).prove_bytes(
+                            assertions_for(st_, 1 << log_steps, 3), [], [3])
+                    _cache[key] = hashlib.sha256(blob).hexdigest()
+                return _cache[key]
+
+            cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(ga, ef, fri, gpu_digest)
+
+            # ---- every BASELINE.json configuration through the product entry (compiled programs, packed seeds), driver-run: wall-clock per
+            # proof, device-busy time and launches per proof (rocprofv3 --kernel-trace of a second child), the reference's own phase log
+            # with device-synchronised times.  Child processes of this run (tools/config_runs.py); N = 1 only
+            configs = None
+            if not args.no_configs and world == 1:
+                import subprocess
+                try:
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'config_runs.py')], capture_output=True, text=True, timeout=600)
+                    configs = json.loads([l for l in r.stdout.splitlines() if l.startswith('[')][-1])
+                except Exception as e:   # noqa: BLE001
+                    configs = [{'error': repr(e)[:300]}]
+            # the kernel that dominates the PROOF (the NTT pass above dominates the transform metric, not the proof): from the C5 run
+            c5 = next((c for c in (configs or []) if c.get('name') == 'C5' and c.get('dominant_kernel')), None)
+            if c5 is not None:
+                ms_k = c5['dominant_kernel_ms_per_proof']
+                fused_leaves = 'k_merkle_fused<1, 1>' in c5['dominant_kernel']
+                comp = n * 1.875 if fused_leaves else None        # 2^24 leaf hashes + the three node layers above them in the same launch
+                roofline['proof_dominant_kernel'] = {
+                    'kernel': c5['dominant_kernel'], 'ms_per_proof': ms_k, 'share_of_device_busy_time': c5['dominant_share'],
+                    'device_busy_ms_per_proof': c5['device_busy_ms'],
+                    'what': 'evaluation-tree commitment: mergeVectorRows + the first three node layers in one launch (lib/Stark.ts:113-118)' if fused_leaves else None,
+                    'bound': 'blake2s compression issue rate (39.5 G compressions/s chip-wide, tools/microbench_hash.hip), not HBM',
+                    'compressions_per_sec': None if comp is None else round(comp / (ms_k * 1e-3), 1),
+                    'frac_of_compression_roof': None if comp is None else round(comp / (ms_k * 1e-3) / 39.5e9, 4),
+                    'algorithmic_GBs': None if comp is None else round(n * (16 + 32 + 28) / (ms_k * 1e-3) / 1e9, 1),
+                    'frac_of_hbm_peak': None if comp is None else round(n * (16 + 32 + 28) / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+            # every kernel of the headline proof and of the long Poseidon proof against its roof (tools/config_runs.py: kernel_table): the
+            # kernel trace of the configuration's own child run joined with the library's tally of what each launch had to move
+            roofline['kernels'] = {c_['name']: c_.pop('kernels') for c_ in (configs or []) if c_.get('name') in ('C5', 'C4_long') and c_.get('kernels')}
+            roofline['kernels_note'] = ('per proof: calls and ms from rocprofv3 --kernel-trace of the configuration\'s child run; algorithmic_MB = the bytes the launches HAD to '
+                                        'read once and write once (gs_traffic_enable: tallied by the library per launch from its arguments — an NTT pass 16 B in + 16 B out '
+                                        'per element, a Merkle layer 64 B in + 32 B out per node, ...); frac_hbm against 8 TB/s; frac_own_roof where the kernel\'s own roof '
+                                        'is known (BLAKE2s compression issue 39.5 G/s; NTT passes: issue time of their static VALU mix)')
+            for c_ in (configs or []):
+                c_.pop('kernels', None)
+            # the reference's phase vocabulary for the headline proof (README.md:62-73; lib/Stark.ts:92-152), device-synchronised
+            prover.sync_phases(True)
+            prover.prove_bytes(a, [], [seed])
+            phases_readme = prover.last_stats().get('phases_readme')
+            prover.sync_phases(False)
+
+            # ---- extra leg (reported beside `value`, never as `value`): throughput of a proving service that keeps several
+            # independent proofs in flight on this GPU (genstark_amd/pipeline.py); every proof runs the unmodified prove()
+            pipelined = None
+            if args.lanes > 0 and world == 1:
+                from genstark_amd.pipeline import ProverPool
+                job = (a, [], [seed])
+                with ProverPool(lambda be: ga.mimcProver(steps, {'hashAlgorithm': 'blake2s256', 'extensionFactor': ef, 'exeQueryCount': 48, 'friQueryCount': fri}, backend=be), lanes=args.lanes,
+                                backend_factory=lambda: Backend(device=device_index), native=True) as pool:
+                    for _ in range(max(args.warmup, 1)):
+                        pool.on_every_lane(lambda s: s.prove_bytes(*job))
+                    tp = time.perf_counter()
+                    proofs = pool.prove_many_bytes([job] * args.lane_proofs)
+                    dt = time.perf_counter() - tp
+                    assert all(pr == data for pr in proofs)                        # same statement -> same bytes as the timed steps
+                pipelined = {'lanes': args.lanes, 'proofs': args.lane_proofs, 'ms_per_proof': round(dt / args.lane_proofs * 1e3, 3),
+                             'value': points * args.lane_proofs / dt, 'unit': 'elements/s',
+                             'note': 'independent proofs in flight on one GPU (one library context + HIP stream per lane): a lane\'s '
+                                     'host-side trace recurrence overlaps the other lanes\' kernels; latency of one proof is prove_ms'}
+            out.update({'python_mirror_prove_ms': mirror_ms, 'roofline': roofline, 'cpu_baseline': cpu, 'pipelined': pipelined,
+                        'phases_readme': {'ms': phases_readme, 'total_ms': None if not phases_readme else round(sum(m for _, m in phases_readme), 4),
+                                          'note': 'the reference\'s own log points (README.md:62-73, lib/Stark.ts:92-152) on ONE extra proof of the headline statement '
+                                                  'with the device synchronised at each of them (gs_prover_sync_phases): each entry is that phase alone; the timed '
+                                                  'proofs above run asynchronously and overlap them (phases_ms)'},
+                        'configs': configs})
     # ---- N > 1.  `value` stays the BASELINE metric on the BASELINE workload with one independent MiMC-128 proof per GPU (weak
     # scaling, no data-path collective: a single MiMC proof is bounded by the serial trace recurrence of its one register, SURVEY 8e
     # "Fallback").  Beside it, the `one_proof` object: ONE proof across all ranks through the native distributed driver
@@ -707,7 +744,7 @@ def main():
     # --sharded-leg-timeout seconds and rank 0 still prints ONE valid line.
     if out is not None and launcher_note:
         out['launcher_note'] = launcher_note
-    if dist is not None and args.sharded_leg_timeout > 0:
+    if dist is not None and args.full and args.sharded_leg_timeout > 0:
         import hashlib
         import threading
         result = {}

@@ -17,8 +17,8 @@ rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ
 cp $O/pmc_sq/s_counter_collection.csv $O/${TAG}_c_pmc_sq_ntt_2p24.csv 2>/dev/null
 python $R/tools/pmc_traffic.py 24 $O > $O/${TAG}_c_ntt_pass_traffic.json 2>&1
 # 3. the benchmark itself: the JSON line, and the kernel trace of the same command
-python $R/bench.py > $O/${TAG}_d_bench_default.json 2> $O/${TAG}_d_bench_default.err
-rocprofv3 --kernel-trace --stats -d $O/trace_bench -o b -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pmc --lanes 0 > $O/${TAG}_e_bench_under_rocprof.json 2>/dev/null
-python $R/tools/rocprof_summary.py $O/trace_bench/b_results.db rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pmc --lanes 0 > $O/${TAG}_e_kernel_stats_bench.md 2>&1
+python $R/bench.py --full > $O/${TAG}_d_bench_default.json 2> $O/${TAG}_d_bench_default.err
+rocprofv3 --kernel-trace --stats -d $O/trace_bench -o b -- python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-pmc --lanes 0 > $O/${TAG}_e_bench_under_rocprof.json 2>/dev/null
+python $R/tools/rocprof_summary.py $O/trace_bench/b_results.db rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-pmc --lanes 0 > $O/${TAG}_e_kernel_stats_bench.md 2>&1
 rm -rf $O/trace_ntt $O/trace_bench $O/pmc_sq
 ls -la $O
