@@ -395,6 +395,33 @@ std::vector<uint64_t> unique_in_order(const std::vector<uint64_t> &v) {
     return out;
 }
 
+// the body of a C entry point: a Fail returns its code (and message), any other exception `other` (and its what())
+template <class Body>
+int guarded(char *err, uint64_t errcap, int other, Body &&body) {
+    try {
+        return body();
+    } catch (const Fail &f) {
+        if (err && errcap) snprintf(err, (size_t)errcap, "%s", f.msg.c_str());
+        return f.code ? f.code : GS_ERR_ARG;
+    } catch (const std::exception &e) {
+        if (err && errcap) snprintf(err, (size_t)errcap, "%s", e.what());
+        return other;
+    }
+}
+// a prove entry point: the serialized proof into out[0..cap); *len receives the size (also when cap is too small: GS_ERR_ARG then)
+template <class Prove>
+int prove_guarded(gs_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *len, char *err, uint64_t errcap, Prove &&prove) {
+    return guarded(err, errcap, GS_ERR_OOM, [&]() -> int {
+        Ctx x{ctx};
+        Bytes proof;
+        prove(x, proof);
+        *len = proof.size();
+        if (proof.size() > cap || !out) return GS_ERR_ARG;
+        memcpy(out, proof.data(), proof.size());
+        return GS_OK;
+    });
+}
+
 }  // namespace
 
 // What the last prove() on this thread did: wall-clock of the phases (host clock at the phase boundaries; no device
@@ -489,21 +516,7 @@ int gs_prover_prove(gs_ctx *ctx, const struct gs_prover_job *job, uint8_t *out, 
 }
 static int prove_entry(gs_ctx *ctx, const struct gs_prover_job *job, uint8_t *out, uint64_t cap, uint64_t *len, char *err, uint64_t errcap) {
     if (!ctx || !job || !len) return GS_ERR_ARG;
-    try {
-        Ctx x{ctx};
-        Bytes proof;
-        prove_impl(x, *job, proof);
-        *len = proof.size();
-        if (proof.size() > cap || !out) return GS_ERR_ARG;
-        memcpy(out, proof.data(), proof.size());
-        return GS_OK;
-    } catch (const Fail &f) {
-        if (err && errcap) snprintf(err, (size_t)errcap, "%s", f.msg.c_str());
-        return f.code ? f.code : GS_ERR_ARG;
-    } catch (const std::exception &e) {
-        if (err && errcap) snprintf(err, (size_t)errcap, "%s", e.what());
-        return GS_ERR_OOM;
-    }
+    return prove_guarded(ctx, out, cap, len, err, errcap, [&](Ctx &x, Bytes &proof) { prove_impl(x, *job, proof); });
 }
 
 static int remainder_check_entry(const uint8_t *values, uint64_t len, uint32_t extension_factor, uint64_t max_degree_plus1, const uint8_t *root_of_unity, int method);
@@ -521,15 +534,11 @@ int gs_prover_remainder_check_on(const gs_prover_binding *b, const uint8_t *valu
 }
 static int remainder_check_entry(const uint8_t *values, uint64_t len, uint32_t extension_factor, uint64_t max_degree_plus1, const uint8_t *root_of_unity, int method) {
     if (!values || !root_of_unity || !len || (method != 0 && method != 1)) return GS_ERR_ARG;
-    try {
+    return guarded(nullptr, 0, GS_ERR_OOM, [&]() -> int {
         std::vector<F> v(len);
         for (uint64_t i = 0; i < len; i++) v[i] = from16(values + ELEM * i);
         return remainder_is_low_degree(v, extension_factor, max_degree_plus1, from16(root_of_unity), method) ? 1 : 0;
-    } catch (const Fail &f) {
-        return f.code ? f.code : GS_ERR_ARG;
-    } catch (const std::exception &) {
-        return GS_ERR_OOM;
-    }
+    });
 }
 
 void gs_prover_sync_phases(int on) { g_sync_phases = on != 0; }
@@ -539,19 +548,13 @@ int gs_prover_abi_version(void) { return GS_PROVER_ABI_VERSION; }
 
 int gs_prover_input_layout(const struct gs_input_register *inputs, uint32_t ninputs, const uint32_t *shapes, uint64_t *length, char *err, uint64_t errcap) {
     if ((ninputs && (!inputs || !shapes)) || !length) return GS_ERR_ARG;
-    try {
+    return guarded(err, errcap, GS_ERR_OOM, [&]() -> int {
         gs_prover_air air;
         memset(&air, 0, sizeof air);
         air.inputs = inputs; air.ninputs = ninputs; air.input_shapes = shapes;
         *length = input_layout(air, job_shapes(air)).length;
         return GS_OK;
-    } catch (const Fail &f) {
-        if (err && errcap) snprintf(err, (size_t)errcap, "%s", f.msg.c_str());
-        return f.code ? f.code : GS_ERR_ARG;
-    } catch (const std::exception &e) {
-        if (err && errcap) snprintf(err, (size_t)errcap, "%s", e.what());
-        return GS_ERR_OOM;
-    }
+    });
 }
 
 int gs_prover_last_stats(struct gs_prover_stats *out) {
@@ -685,6 +688,205 @@ static bool remainder_is_low_degree(const std::vector<F> &remainder, uint64_t E,
     return true;
 }
 
+namespace {
+
+// ---- the statement plan: what both provers and the verifier derive from the statement and must agree on to the byte ----------
+// compositionFactor = 2^ceil(log2(max constraint degree))
+uint64_t composition_factor(const gs_prover_air &air) {
+    uint32_t max_degree = 1;
+    for (uint32_t i = 0; i < air.nconstraints; i++) max_degree = std::max(max_degree, air.degrees[i]);
+    uint64_t cf = 1;
+    while (cf < max_degree) cf <<= 1;
+    return cf;
+}
+// FiniteField.interpolate(xs, ys) for the handful of points of an assertion set (the library's gs_small_interpolate): coefficients as
+// bytes at `out`, or as elements
+void interpolate(const std::vector<F> &xs, const std::vector<F> &ys, uint8_t *out) {
+    const size_t n = xs.size();
+    Bytes xb(n * ELEM), yb(n * ELEM);
+    for (size_t i = 0; i < n; i++) { le16(xs[i], xb.data() + ELEM * i); le16(ys[i], yb.data() + ELEM * i); }
+    if (A.gs_small_interpolate(xb.data(), yb.data(), (uint32_t)n, out)) fail(GS_ERR_ARG, "gs_small_interpolate failed");
+}
+std::vector<F> lagrange(const std::vector<F> &xs, const std::vector<F> &ys) {
+    Bytes cb(xs.size() * ELEM);
+    interpolate(xs, ys, cb.data());
+    std::vector<F> out(xs.size());
+    for (size_t i = 0; i < out.size(); i++) out[i] = from16(cb.data() + ELEM * i);
+    return out;
+}
+Bytes pack(const std::vector<F> &v, size_t from, size_t count) {
+    Bytes b(count * ELEM);
+    for (size_t i = 0; i < count; i++) le16(v[from + i], b.data() + ELEM * i);
+    return b;
+}
+std::vector<uint64_t> augmented_rows(const std::vector<uint64_t> &positions, uint64_t column_length) {      // LowDegreeProver.ts:302-309
+    std::vector<uint64_t> out;
+    for (uint64_t p : positions) out.push_back(p % (column_length / 4));
+    return unique_in_order(out);
+}
+
+struct Plan {
+    uint64_t T, E, N;
+    F omega;                                            // generator of the evaluation domain (N points)
+    uint64_t cf, Nc, combination_degree, composition_degree, b_inc;     // CompositionPolynomial.ts:196-204
+    uint32_t exe_query_count, fri_query_count;
+    // boundary constraints per asserted register, in order of first appearance (BoundaryConstraints.ts:15-45)
+    struct Reg { uint32_t reg; std::vector<uint64_t> steps; std::vector<F> xs, ys; };
+    std::vector<Reg> regs;
+    // constraints grouped by degree (times T), in order of first appearance (CompositionPolynomial.ts:206-225)
+    std::vector<std::pair<uint64_t, std::vector<uint32_t>>> groups;
+    uint32_t dcount, bcoef;                              // coefficients of Q's terms, of the boundary terms
+
+    // the coefficient stream from the evaluation root (lib/Stark.ts:121): dcount for Q, bcoef for B, then lccount(V) for the linear
+    // combination of V committed vectors (LinearCombination.ts:58-59)
+    uint32_t lccount(uint32_t V) const { return b_inc > 0 ? 2 * V : V; }
+    std::vector<F> coefficients(const Bytes &root, uint32_t V) const { return prng_many(root, dcount + bcoef + lccount(V)); }
+
+    // the product of (x - x_i) over a register's assertions (BoundaryConstraints.ts:24-30)
+    std::vector<F> zero_poly(const Reg &r) const {
+        std::vector<F> zp{(F)1};
+        for (F xi : r.xs) {
+            std::vector<F> nz(zp.size() + 1, (F)0);
+            const F nx = hf_sub(0, xi);
+            for (size_t k = 0; k < zp.size(); k++) { nz[k] = hf_add(nz[k], hf_mul(zp[k], nx)); nz[k + 1] = hf_add(nz[k + 1], zp[k]); }
+            zp.swap(nz);
+        }
+        return zp;
+    }
+    // the asserted registers as rows of `width` (the most assertions on one register) for the boundary kernels: where each assertion's
+    // point lies, in units of the domain's generator (step * unit), the count per row and — with_interpolants — each row's interpolant
+    struct Boundary {
+        uint32_t width = 0;
+        std::vector<uint64_t> at;
+        std::vector<uint32_t> per_row;
+        Bytes interpolants;
+    };
+    Boundary boundary(uint64_t unit, bool with_interpolants) const {
+        Boundary b;
+        for (auto &r : regs) b.width = std::max(b.width, (uint32_t)r.steps.size());
+        b.at.assign(regs.size() * b.width, 0);
+        b.per_row.resize(regs.size());
+        if (with_interpolants) b.interpolants.assign(regs.size() * b.width * ELEM, 0);
+        for (size_t r = 0; r < regs.size(); r++) {
+            b.per_row[r] = (uint32_t)regs[r].steps.size();
+            for (size_t k = 0; k < regs[r].steps.size(); k++) b.at[r * b.width + k] = regs[r].steps[k] * unit;
+            if (with_interpolants) interpolate(regs[r].xs, regs[r].ys, b.interpolants.data() + r * b.width * ELEM);    // BoundaryConstraints.ts:42
+        }
+        return b;
+    }
+
+    // query positions (lib/Stark.ts:146-152, QueryIndexGenerator.ts:28-32) from the root of the linear combination's tree ...
+    std::vector<uint64_t> exe_positions(const Bytes &lc_root) const {
+        return query_indexes(lc_root, (uint32_t)std::min<uint64_t>(exe_query_count, N - N / E), N, (uint32_t)E);
+    }
+    // ... the leaves of the evaluation tree they open: each position and its next step (lib/Stark.ts:274-296) ...
+    std::vector<uint64_t> evaluation_positions(const std::vector<uint64_t> &positions) const {
+        std::vector<uint64_t> aug;
+        for (uint64_t p : positions) { aug.push_back(p); aug.push_back((p + E) % N); }
+        return unique_in_order(aug);
+    }
+    // ... and per FRI layer, from the root of its column's tree: positions in the column, the rows of the column's tree (:209-219)
+    struct Queries { std::vector<uint64_t> positions, rows; };
+    Queries layer_queries(const Bytes &column_root, uint64_t column_length) const {
+        Queries q;
+        q.positions = query_indexes(column_root, fri_query_count, column_length, (uint32_t)E);
+        q.rows = augmented_rows(q.positions, column_length);
+        return q;
+    }
+};
+// the trace of T steps at extension factor E, omega of order T E
+Plan make_plan(const gs_prover_job &job, uint64_t T, uint64_t E, F omega) {
+    const gs_prover_air &air = job.air;
+    Plan p;
+    p.T = T; p.E = E; p.N = T * E; p.omega = omega;
+    p.cf = composition_factor(air);
+    p.Nc = T * p.cf;
+    p.combination_degree = p.cf * T;
+    p.composition_degree = std::max(p.combination_degree - T, T);
+    p.b_inc = p.composition_degree - T;
+    p.exe_query_count = job.exe_query_count;
+    p.fri_query_count = job.fri_query_count;
+    for (uint32_t i = 0; i < job.nassertions; i++) {
+        const gs_assertion &a = job.assertions[i];
+        Plan::Reg *r = nullptr;
+        for (auto &e : p.regs) if (e.reg == a.reg) r = &e;
+        if (!r) { p.regs.push_back(Plan::Reg{a.reg, {}, {}, {}}); r = &p.regs.back(); }
+        r->steps.push_back(a.step);
+        r->xs.push_back(hf_pow(omega, (hfe)(a.step * E)));
+        r->ys.push_back(from16(a.value));
+    }
+    for (uint32_t i = 0; i < air.nconstraints; i++) {
+        const uint64_t d = (uint64_t)air.degrees[i] * T;
+        bool found = false;
+        for (auto &g : p.groups) if (g.first == d) { g.second.push_back(i); found = true; }
+        if (!found) p.groups.push_back({d, {i}});
+    }
+    p.dcount = air.nconstraints;
+    for (auto &g : p.groups) if (g.first < p.combination_degree) p.dcount += (uint32_t)g.second.size();
+    p.bcoef = (uint32_t)p.regs.size() * (p.composition_degree > T ? 2 : 1);
+    return p;
+}
+
+// Q = every constraint's plain term + each group's degree-adjusted terms (CompositionPolynomial.ts:83-107), n values per vector:
+// gs_combine_adjusted merges sum k_i q_i + powers o sum k'_i q_i in one pass, the adjusted vectors are not materialised (one further
+// pass per additional group of a degree of its own: different powers).  powers(e) gives x^e over the same n points
+template <class Powers>
+void merge_q(Ctx &x, const Plan &plan, const std::vector<F> &co, const std::vector<const void *> &qa, uint64_t n, Powers &&powers, void *merged) {
+    const uint32_t nq = (uint32_t)qa.size();
+    Bytes plain = pack(co, 0, nq);
+    uint32_t next = nq;                                      // coefficients of the adjusted terms follow, group by group
+    bool first = true;
+    for (auto &g : plan.groups) {
+        if (g.first == plan.combination_degree) continue;
+        Buf pw = powers(plan.combination_degree - g.first);
+        if (first) {                                         // every constraint's plain term + this group's adjusted terms
+            Bytes adj(nq * ELEM, 0);
+            for (uint32_t i : g.second) le16(co[next++], adj.data() + ELEM * i);
+            x.check(A.gs_combine_adjusted(x.c, qa.data(), plain.data(), adj.data(), nq, pw.p, nullptr, n, merged), "gs_combine_adjusted(Q)");
+        } else {
+            std::vector<const void *> members;
+            Bytes adj(g.second.size() * ELEM);
+            for (size_t k = 0; k < g.second.size(); k++) { members.push_back(qa[g.second[k]]); le16(co[next++], adj.data() + ELEM * k); }
+            x.check(A.gs_combine_adjusted(x.c, members.data(), nullptr, adj.data(), (uint32_t)members.size(), pw.p, merged, n, merged), "gs_combine_adjusted(Q)");
+        }
+        first = false;
+    }
+    if (first) x.check(A.gs_combine_many(x.c, qa.data(), plain.data(), nq, n, merged), "gs_combine_many(Q)");
+}
+
+// LowDegreeProver.verifyRemainder (:223-252) for a prover: the remainder after `depth` layers lies on the powers of omega^(4^depth)
+void check_remainder(const Plan &plan, const std::vector<F> &remainder, uint32_t depth) {
+    F rou = plan.omega;
+    uint64_t max_degree_plus1 = plan.composition_degree;
+    for (uint32_t d = 0; d < depth; d++) { rou = hf_mul(rou, rou); rou = hf_mul(rou, rou); max_degree_plus1 /= 4; }
+    if (!remainder_is_low_degree(remainder, plan.E, max_degree_plus1, rou, 1))
+        fail(GS_ERR_ARG, "Low degree proof failed: Remainder is not a valid degree %llu polynomial", (unsigned long long)(max_degree_plus1 - 1));
+}
+
+// Serializer.serializeProof (:35-79)
+struct Component { Bytes columnRoot; MerkleProof columnProof, polyProof; };
+void write_proof(Bytes &out, const Bytes &evRoot, const MerkleProof &evProof, uint32_t V, const Bytes &lcRoot, const MerkleProof &lcProof,
+                 const std::vector<Component> &components, const std::vector<F> &remainder, const Shapes &input_shapes) {
+    out.clear();
+    out.insert(out.end(), evRoot.begin(), evRoot.end());
+    write_merkle_proof(out, evProof, (uint64_t)V * ELEM);
+    out.insert(out.end(), lcRoot.begin(), lcRoot.end());
+    write_merkle_proof(out, lcProof, 4 * ELEM);
+    if (components.size() > 255) fail(GS_ERR_ARG, "too many FRI components");
+    out.push_back((uint8_t)components.size());
+    for (auto &c : components) {
+        out.insert(out.end(), c.columnRoot.begin(), c.columnRoot.end());
+        write_merkle_proof(out, c.columnProof, 4 * ELEM);
+        write_merkle_proof(out, c.polyProof, 4 * ELEM);
+    }
+    if (remainder.size() > MAX_ARRAY) fail(GS_ERR_ARG, "remainder too long");
+    out.push_back(remainder.size() == MAX_ARRAY ? 0 : (uint8_t)remainder.size());
+    for (F v : remainder) { uint8_t b[ELEM]; le16(v, b); out.insert(out.end(), b, b + ELEM); }
+    write_input_shapes(out, input_shapes);
+}
+
+}  // namespace
+
 static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     PhaseClock clock;
     const gs_prover_air &air = job.air;
@@ -693,13 +895,10 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     const int alg = job.hash_alg;
     if (!T || (T & (T - 1)) || !E || (E & (E - 1)) || !R || !air.nconstraints || !job.nassertions) fail(GS_ERR_ARG, "invalid job");
     const Shapes input_shapes = checked_job_shapes(job);          // iShapes of the proof (lib/Stark.ts:161); empty without input registers
-    uint32_t max_degree = 1;
-    for (uint32_t i = 0; i < air.nconstraints; i++) max_degree = std::max(max_degree, air.degrees[i]);
-    uint64_t cf = 1;
-    while (cf < max_degree) cf <<= 1;                              // compositionFactor = 2^ceil(log2(max degree))
-    const uint64_t Nc = T * cf;
-    if (E < 2 * cf) fail(GS_ERR_ARG, "extension factor must be at least 2x the composition factor");
+    if (E < 2 * composition_factor(air)) fail(GS_ERR_ARG, "extension factor must be at least 2x the composition factor");
     const F omega = domain_root(job, N);
+    const Plan plan = make_plan(job, T, E, omega);
+    const uint64_t Nc = plan.Nc, combination_degree = plan.combination_degree, b_inc = plan.b_inc;
     const F comp_rou = hf_pow(omega, (hfe)(N / Nc)), exec_rou = hf_pow(omega, (hfe)E);
     uint8_t s16[ELEM], s16b[ELEM];
 
@@ -708,8 +907,6 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
 
     // work of CompositionPolynomial.evaluateAll that does not depend on the trace goes first: the device computes it while
     // the host core below runs the trace recurrence (same values, issue order only)
-    const uint64_t combination_degree = cf * T;                                        // CompositionPolynomial.ts:196-204
-    const uint64_t composition_degree = std::max(combination_degree - T, T);
     // MiMC with up to four assertions: the whole of CompositionPolynomial.evaluateAll is one kernel over the evaluation domain
     // (gs_mimc_composition, below); otherwise the member-by-member sequence, whose trace-independent part is issued here
     uint32_t assertions_on_r0 = 0;
@@ -739,7 +936,6 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         }
     }
     Buf psbPowers;                                                 // x^(compositionDegree - T) over the evaluation domain
-    const uint64_t b_inc = composition_degree - T;
     const bool lc_folds = fused && R + air.nsecret == 1;           // LinearCombination folded into the composition kernel too
     if (b_inc > 0 && !lc_folds && !tail) {                         // also what LinearCombination.ts:44-52 multiplies by
         psbPowers = Buf(x, N * ELEM);
@@ -805,30 +1001,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     clock.mark("P(x), extension, evaluation tree issued");
     clock.readme(x, "Serialized evaluations of P(x) and S(x) polynomials + Built evaluation merkle tree (one fused call)");
     // 5 ----- composition polynomial (CompositionPolynomial.ts:29-146)
-    // boundary constraints per asserted register, in order of first appearance (BoundaryConstraints.ts:15-45)
-    struct RegData { uint32_t reg; std::vector<F> xs, ys; std::vector<uint64_t> at; };   // at: positions of the xs in the evaluation domain
-    std::vector<RegData> rdata;
-    for (uint32_t i = 0; i < job.nassertions; i++) {
-        const gs_assertion &a = job.assertions[i];
-        RegData *d = nullptr;
-        for (auto &e : rdata) if (e.reg == a.reg) d = &e;
-        if (!d) { rdata.push_back(RegData{a.reg, {}, {}, {}}); d = &rdata.back(); }
-        d->at.push_back(a.step * E);
-        d->xs.push_back(hf_pow(omega, (hfe)(a.step * E)));
-        d->ys.push_back(from16(a.value));
-    }
-    const uint32_t bcount = (uint32_t)rdata.size();
-    // constraint groups by degree, in order of first appearance (:206-225)
-    std::vector<std::pair<uint64_t, std::vector<uint32_t>>> groups;
-    for (uint32_t i = 0; i < air.nconstraints; i++) {
-        uint64_t d = (uint64_t)air.degrees[i] * T;
-        bool found = false;
-        for (auto &g : groups) if (g.first == d) { g.second.push_back(i); found = true; }
-        if (!found) groups.push_back({d, {i}});
-    }
-    uint32_t dcount = air.nconstraints;
-    for (auto &g : groups) if (g.first < combination_degree) dcount += (uint32_t)g.second.size();
-    uint32_t bcoef = bcount * (composition_degree > T ? 2 : 1);
+    const uint32_t bcount = (uint32_t)plan.regs.size(), dcount = plan.dcount, bcoef = plan.bcoef;
     // The coefficients come from the evaluation root (:121): it is read where the first of them is needed, with the asserted cells —
     // the work that needs neither (constraint evaluation, degree adjustment) is queued first and covers the round trip
     std::vector<F> coefficients;
@@ -844,43 +1017,29 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
                 fail(GS_ERR_ARG, "Assertion at step %llu, register %u conflicts with execution trace", (unsigned long long)job.assertions[i].step,
                      job.assertions[i].reg);
         trace.release();
-        coefficients = prng_many(eTree.root, dcount + bcoef);
-    };
-    auto coeff_bytes = [&](size_t from, size_t count) {
-        Bytes b(count * ELEM);
-        for (size_t i = 0; i < count; i++) le16(coefficients[from + i], b.data() + ELEM * i);
-        return b;
+        coefficients = plan.coefficients(eTree.root, V);
     };
 
     Buf cEval(x, N * ELEM);
     bool lc_fused = false;                     // cEval already holds L (LinearCombination folded into the composition kernel)
     if (fused) {
-        // K over the evaluation domain (issued before the trace), the interpolant through the assertions, then one kernel for :71-146
-        // (what needs no coefficient first: the device is idle while the root travels)
-        const RegData &d = rdata[0];
-        const uint32_t m = (uint32_t)d.xs.size();
-        Bytes xs(m * ELEM), ys(m * ELEM), ipoly(m * ELEM);
-        for (uint32_t i = 0; i < m; i++) { le16(d.xs[i], xs.data() + ELEM * i); le16(d.ys[i], ys.data() + ELEM * i); }
-        if (A.gs_small_interpolate(xs.data(), ys.data(), m, ipoly.data())) fail(GS_ERR_ARG, "gs_small_interpolate failed");    // BoundaryConstraints.ts:42
+        // K over the evaluation domain (issued before the trace), the interpolant through the assertions (all on register 0: one row
+        // of the boundary plan), then one kernel for :71-146 (what needs no coefficient first: the device is idle while the root travels)
+        const Plan::Boundary bd = plan.boundary(E, true);
         read_evaluation_root();
-        const bool q_adjusted = groups[0].first < combination_degree;
+        const bool q_adjusted = plan.groups[0].first < combination_degree;
         Bytes co(4 * ELEM, 0);
         le16(coefficients[0], co.data());
         if (q_adjusted) le16(coefficients[1], co.data() + ELEM);
         le16(coefficients[dcount], co.data() + 2 * ELEM);
         if (b_inc > 0) le16(coefficients[dcount + 1], co.data() + 3 * ELEM);
         // ... and, with one committed vector, LinearCombination.computeMany (:36-64) on top: the same prng stream continues
-        const bool with_lc = lc_folds;
-        Bytes lc(2 * ELEM, 0);
-        if (with_lc) {
-            std::vector<F> all = prng_many(eTree.root, dcount + bcoef + (b_inc > 0 ? 2 : 1));
-            le16(all[dcount + bcoef], lc.data());
-            if (b_inc > 0) le16(all[dcount + bcoef + 1], lc.data() + ELEM);
-        }
-        lc_fused = with_lc;
+        lc_fused = lc_folds;
+        Bytes lc = lc_folds ? pack(coefficients, dcount + bcoef, plan.lccount(V)) : Bytes();
+        lc.resize(2 * ELEM, 0);                                    // (the kernel reads two; the second is 0 without a degree adjustment)
         le16(omega, s16);
-        x.check(A.gs_mimc_composition(x.c, pRows[0], N, T, s16, kN.p, klen_n, co.data(), q_adjusted ? combination_degree - groups[0].first : 0, b_inc,
-                                      ipoly.data(), d.at.data(), m, with_lc ? lc.data() : nullptr, cEval.p), "gs_mimc_composition");
+        x.check(A.gs_mimc_composition(x.c, pRows[0], N, T, s16, kN.p, klen_n, co.data(), q_adjusted ? combination_degree - plan.groups[0].first : 0, b_inc,
+                                      bd.interpolants.data(), bd.at.data(), bd.per_row[0], lc_folds ? lc.data() : nullptr, cEval.p), "gs_mimc_composition");
     } else {
         // 5.1-5.3: the combined, degree-adjusted Q has degree < Nc, so its extension to the evaluation domain (:109-110) is what
         // the constraint expression gives there.  MiMC (one cheap constraint): evaluate it on all N points from the extension of P
@@ -898,38 +1057,18 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
             x.check(A.gs_air_constraints_strided(x.c, air.e_code, air.e_ninstr, air.consts, air.nconsts, air.vm_regs, R, air.nconstraints, pEval.p, N, N / Nc,
                                                  Nc, Nc / T, air.static_tables, air.static_lens, air.nstatic, q.p), "gs_air_constraints_strided");
         }
-        // 5.2 degree adjustment (:83-101) and 5.3 merge + extension (:103-111): the adjusted vectors q_i o powers are not
-        // materialised — gs_combine_adjusted merges sum k_i q_i + powers o sum k'_i q_i in one pass (one further pass per additional
-        // group of constraints with a degree of its own: different powers)
+        // 5.2 degree adjustment (:83-101) and 5.3 merge + extension (:103-111)
         std::vector<const void *> qa;
         for (uint32_t i = 0; i < air.nconstraints; i++) qa.push_back(q.at((uint64_t)i * Nq * ELEM));
         read_evaluation_root();
         Buf qe(x, N * ELEM), qc;
         if (!direct) qc = Buf(x, Nc * ELEM);
-        void *merged = direct ? qe.p : qc.p;
-        {
-            Bytes plain = coeff_bytes(0, air.nconstraints);
-            uint32_t next = air.nconstraints;                       // coefficients of the adjusted terms follow, group by group
-            bool first = true;
-            for (auto &g : groups) {
-                if (g.first == combination_degree) continue;
-                Buf powers(x, Nq * ELEM);
-                le16(hf_pow(q_rou, (hfe)(combination_degree - g.first)), s16);
-                x.check(A.gs_power_series(x.c, s16, Nq, powers.p), "gs_power_series(q powers)");
-                if (first) {                                         // every constraint's plain term + this group's adjusted terms
-                    Bytes adj(air.nconstraints * ELEM, 0);
-                    for (uint32_t i : g.second) le16(coefficients[next++], adj.data() + ELEM * i);
-                    x.check(A.gs_combine_adjusted(x.c, qa.data(), plain.data(), adj.data(), air.nconstraints, powers.p, nullptr, Nq, merged), "gs_combine_adjusted(Q)");
-                } else {
-                    std::vector<const void *> members;
-                    Bytes adj(g.second.size() * ELEM);
-                    for (size_t k = 0; k < g.second.size(); k++) { members.push_back(qa[g.second[k]]); le16(coefficients[next++], adj.data() + ELEM * k); }
-                    x.check(A.gs_combine_adjusted(x.c, members.data(), nullptr, adj.data(), (uint32_t)members.size(), powers.p, merged, Nq, merged), "gs_combine_adjusted(Q)");
-                }
-                first = false;
-            }
-            if (first) x.check(A.gs_combine_many(x.c, qa.data(), plain.data(), air.nconstraints, Nq, merged), "gs_combine_many(Q)");
-        }
+        merge_q(x, plan, coefficients, qa, Nq, [&](uint64_t e) {
+            Buf powers(x, Nq * ELEM);
+            le16(hf_pow(q_rou, (hfe)e), s16);
+            x.check(A.gs_power_series(x.c, s16, Nq, powers.p), "gs_power_series(q powers)");
+            return powers;
+        }, direct ? qe.p : qc.p);
         if (!direct) {
             Buf qcPoly(x, Nc * ELEM);
             le16(comp_rou, s16);
@@ -939,63 +1078,25 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         }
         // 5.4-5.7 and 6 in ONE pass (gs_composition_tail): D = Q / Z, the boundary quotients from the registers' extensions, their
         // degree-adjusted merge, and LinearCombination.computeMany on top — when the assertions fit its per-register limits
-        size_t tail_roots = 0;
-        for (auto &d : rdata) tail_roots = std::max(tail_roots, d.at.size());
+        std::vector<const void *> pv;                                      // the asserted registers' extensions
+        for (auto &r : plan.regs) pv.push_back(pRows[r.reg]);
+        const Bytes bco = pack(coefficients, dcount, bcoef);
         if (tail) {
-            const uint32_t il = (uint32_t)tail_roots;                   // an interpolant through m assertions has m coefficients
-            Bytes ip((size_t)bcount * il * ELEM, 0);
-            std::vector<uint64_t> at((size_t)bcount * il, 0);
-            std::vector<uint32_t> per_row(bcount);
-            for (uint32_t r = 0; r < bcount; r++) {
-                const RegData &d = rdata[r];
-                const uint32_t m = (uint32_t)d.xs.size();
-                Bytes xs(m * ELEM), ys(m * ELEM);
-                for (uint32_t i = 0; i < m; i++) { le16(d.xs[i], xs.data() + ELEM * i); le16(d.ys[i], ys.data() + ELEM * i); }
-                if (A.gs_small_interpolate(xs.data(), ys.data(), m, ip.data() + (size_t)r * il * ELEM)) fail(GS_ERR_ARG, "gs_small_interpolate failed");   // BoundaryConstraints.ts:42
-                per_row[r] = m;
-                for (uint32_t k = 0; k < m; k++) at[(size_t)r * il + k] = d.at[k];
-            }
-            std::vector<const void *> pv;
-            for (auto &d : rdata) pv.push_back(pRows[d.reg]);
-            Bytes bco = coeff_bytes(dcount, bcoef);
-            const uint32_t offset = dcount + bcoef, cnt = b_inc > 0 ? 2 * V : V;
-            std::vector<F> co = prng_many(eTree.root, offset + cnt);      // LinearCombination.ts:36-64: the same stream continues
-            Bytes cb(cnt * ELEM);
-            for (uint32_t i = 0; i < cnt; i++) le16(co[offset + i], cb.data() + ELEM * i);
+            const Plan::Boundary bd = plan.boundary(E, true);              // an interpolant through m assertions has m coefficients
+            const Bytes cb = pack(coefficients, dcount + bcoef, plan.lccount(V));      // LinearCombination.ts:36-64: the same stream continues
             le16(omega, s16);
             le16(hf_pow(omega, (hfe)((T - 1) * E)), s16b);                                           // ZeroPolynomial.ts:21-23: the last step's point
-            x.check(A.gs_composition_tail(x.c, N, s16, qe.p, tail_makes_z ? nullptr : zInverses.p, T, s16b, pv.data(), bcount, ip.data(), il, at.data(),
-                                          per_row.data(), il, bco.data(), b_inc > 0 ? bco.data() + ELEM * bcount : nullptr, eVectors.data(), V, cb.data(),
-                                          b_inc > 0 ? cb.data() + ELEM * V : nullptr, nullptr, b_inc, nullptr, cEval.p), "gs_composition_tail");
+            x.check(A.gs_composition_tail(x.c, N, s16, qe.p, tail_makes_z ? nullptr : zInverses.p, T, s16b, pv.data(), bcount, bd.interpolants.data(), bd.width,
+                                          bd.at.data(), bd.per_row.data(), bd.width, bco.data(), b_inc > 0 ? bco.data() + ELEM * bcount : nullptr, eVectors.data(), V,
+                                          cb.data(), b_inc > 0 ? cb.data() + ELEM * V : nullptr, nullptr, b_inc, nullptr, cEval.p), "gs_composition_tail");
             lc_fused = true;
         } else {
         // 5.4 D(x) = Q(x) / Z(x) (:113-121)
         Buf dEval(x, N * ELEM);
         x.check(A.gs_vec_mul(x.c, qe.p, zInverses.p, N, dEval.p), "gs_vec_mul(D)");
         // 5.5 boundary constraints (BoundaryConstraints.ts:71-95)
-        size_t ilen = 0, zlen = 0;
         std::vector<std::vector<F>> ipolys, zpolys;
-        for (auto &d : rdata) {
-            const uint32_t m = (uint32_t)d.xs.size();
-            Bytes xs(m * ELEM), ys(m * ELEM), co(m * ELEM);
-            for (uint32_t i = 0; i < m; i++) { le16(d.xs[i], xs.data() + ELEM * i); le16(d.ys[i], ys.data() + ELEM * i); }
-            if (A.gs_small_interpolate(xs.data(), ys.data(), m, co.data())) fail(GS_ERR_ARG, "gs_small_interpolate failed");
-            std::vector<F> ip(m), zp{1};
-            for (uint32_t i = 0; i < m; i++) ip[i] = from16(co.data() + ELEM * i);
-            for (uint32_t i = 0; i < m; i++) {          // zPoly *= (x - xs[i]), BoundaryConstraints.ts:24-30
-                std::vector<F> nz(zp.size() + 1, 0);
-                const F nx = hf_sub(0, d.xs[i]);
-                for (size_t k = 0; k < zp.size(); k++) {
-                    nz[k] = hf_add(nz[k], hf_mul(zp[k], nx));
-                    nz[k + 1] = hf_add(nz[k + 1], zp[k]);
-                }
-                zp.swap(nz);
-            }
-            ilen = std::max(ilen, ip.size());
-            zlen = std::max(zlen, zp.size());
-            ipolys.push_back(ip);
-            zpolys.push_back(zp);
-        }
+        for (auto &r : plan.regs) { ipolys.push_back(lagrange(r.xs, r.ys)); zpolys.push_back(plan.zero_poly(r)); }
         auto upload_rows = [&](const std::vector<std::vector<F>> &rows, size_t len) {
             Bytes host(rows.size() * len * ELEM, 0);                    // shorter rows are zero-extended (newMatrixFromVectors)
             for (size_t r = 0; r < rows.size(); r++)
@@ -1004,25 +1105,17 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
             x.check(A.gs_upload(x.c, b.p, host.data(), host.size()), "gs_upload(boundary polynomials)");
             return b;
         };
+        const Plan::Boundary bd = plan.boundary(E, false);
+        const uint32_t ilen = bd.width, zlen = bd.width + 1;              // m assertions: m interpolant coefficients, m + 1 of Z_r
         Buf iPolys = upload_rows(ipolys, ilen);
         Buf iValues(x, (uint64_t)bcount * N * ELEM), pi(x, (uint64_t)bcount * N * ELEM), bEval(x, (uint64_t)bcount * N * ELEM);
         le16(omega, s16);
         x.check(counted_eval_polys_at_roots(x.c, iPolys.p, bcount, ilen, s16, N, iValues.p), "gs_eval_polys_at_roots(I)");
-        std::vector<const void *> pv;
-        for (auto &d : rdata) pv.push_back(pRows[d.reg]);
         x.check(A.gs_sub_matrix_from_vectors(x.c, pv.data(), iValues.p, bcount, N, pi.p), "gs_sub_matrix_from_vectors");
-        size_t max_roots = 0;
-        for (auto &d : rdata) max_roots = std::max(max_roots, d.at.size());
-        if (max_roots <= 4) {
+        if (bd.width <= 4) {
             // the divisors' roots are domain points: look-ups in the domain's table 1/(omega^j - 1) instead of evaluating Z_r(x)
             // and inverting it (same values: BoundaryConstraints.ts:88,92)
-            std::vector<uint64_t> at(bcount * max_roots, 0);
-            std::vector<uint32_t> per_row(bcount);
-            for (uint32_t r = 0; r < bcount; r++) {
-                per_row[r] = (uint32_t)rdata[r].at.size();
-                for (size_t k = 0; k < rdata[r].at.size(); k++) at[r * max_roots + k] = rdata[r].at[k];
-            }
-            x.check(A.gs_div_by_domain_roots(x.c, pi.p, bcount, N, s16, at.data(), per_row.data(), (uint32_t)max_roots, bEval.p), "gs_div_by_domain_roots");
+            x.check(A.gs_div_by_domain_roots(x.c, pi.p, bcount, N, s16, bd.at.data(), bd.per_row.data(), bd.width, bEval.p), "gs_div_by_domain_roots");
         } else {
             Buf zPolys = upload_rows(zpolys, zlen), zValues(x, (uint64_t)bcount * N * ELEM);
             x.check(counted_eval_polys_at_roots(x.c, zPolys.p, bcount, zlen, s16, N, zValues.p), "gs_eval_polys_at_roots(Zb)");
@@ -1032,7 +1125,6 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         // 5.6 degree adjustment of B (:124-138) and 5.7 merge (:140-146), with D added in the same pass
         std::vector<const void *> ba;
         for (uint32_t i = 0; i < bcount; i++) ba.push_back(bEval.at((uint64_t)i * N * ELEM));
-        Bytes bco = coeff_bytes(dcount, bcoef);
         x.check(A.gs_combine_adjusted(x.c, ba.data(), bco.data(), b_inc > 0 ? bco.data() + ELEM * bcount : nullptr, bcount, b_inc > 0 ? psbPowers.p : nullptr,
                                       dEval.p, N, cEval.p), "gs_combine_adjusted(B + D)");
         }
@@ -1048,10 +1140,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     } else {
         lEval = Buf(x, N * ELEM);
         // psIncrementalDegree = compositionDegree - T: the same powers as B's; P_r o powers is not materialised, C is added in the pass
-        const uint32_t offset = dcount + bcoef, cnt = b_inc > 0 ? 2 * V : V;
-        std::vector<F> co = prng_many(eTree.root, offset + cnt);
-        Bytes cb(cnt * ELEM);
-        for (uint32_t i = 0; i < cnt; i++) le16(co[offset + i], cb.data() + ELEM * i);
+        const Bytes cb = pack(coefficients, dcount + bcoef, plan.lccount(V));
         x.check(A.gs_combine_adjusted(x.c, eVectors.data(), cb.data(), b_inc > 0 ? cb.data() + ELEM * V : nullptr, V, b_inc > 0 ? psbPowers.p : nullptr, cEval.p, N,
                                       lEval.p), "gs_combine_adjusted(L)");
     }
@@ -1083,7 +1172,6 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     Tree *pTree = &pTree0;
     const void *column_src = lEval.p;   // the current layer's values in natural order (the remainder at the end)
     uint64_t len = N;
-    uint64_t max_degree_plus1 = composition_degree;
     uint32_t depth = 0;
     layers.reserve(32);
     // every layer's buffers first, then ONE call for the whole recursion (gs_fri_layers = per layer gs_fri_fold_at :189-198 +
@@ -1105,7 +1193,6 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         column_src = L.next.p;
         pTree = &L.cTree;
         len = rows;
-        max_degree_plus1 /= 4;
         depth++;
     }
     if (!layers.empty()) {
@@ -1122,24 +1209,17 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     // Everything the proof reads back — the queried rows and their batch proofs of every tree, the remainder (:179-187: the natural-
     // order vector the last polyValues came from) — is requested in ONE deferral window; the requests are planned root by root as
     // the roots arrive, the window closes with the single synchronisation of the proof
-    struct Component { Bytes columnRoot; MerkleProof columnProof, polyProof; };
     std::vector<Component> components(layers.size());
     Readbacks rb;
     DeferWindow win(x);
     // spot checks of the evaluation tree (lib/Stark.ts:146-152, 274-296) and of the linear combination (LowDegreeProver.ts:52-54,
     // 302-309): positions from the root of the first FRI tree
     await_root(tickets[0], pTree0);
-    const uint32_t exe_count = (uint32_t)std::min<uint64_t>(job.exe_query_count, N - N / E);
-    const std::vector<uint64_t> exe_positions = query_indexes(pTree0.root, exe_count, N, (uint32_t)E);   // QueryIndexGenerator.ts:28-32
-    std::vector<uint64_t> lc_positions;
-    for (uint64_t p : exe_positions) lc_positions.push_back(p % (N / 4));
-    lc_positions = unique_in_order(lc_positions);
+    const std::vector<uint64_t> exe_positions = plan.exe_positions(pTree0.root), lc_positions = augmented_rows(exe_positions, N);
     MerkleProof lcProof;
     rb.prove_batch(x, pTree0, lc_positions, &lcProof);
     rb.gather_rows4(x, lEval.p, N / 4, lc_positions, &lcProof);
-    std::vector<uint64_t> aug;
-    for (uint64_t p : exe_positions) { aug.push_back(p); aug.push_back((p + E) % N); }
-    aug = unique_in_order(aug);
+    const std::vector<uint64_t> aug = plan.evaluation_positions(exe_positions);
     MerkleProof evProof;
     rb.prove_batch(x, eTree, aug, &evProof);
     // the leaves of the evaluation tree are the committed vectors' elements side by side (lib/Stark.ts:284-296)
@@ -1150,16 +1230,13 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         Layer &L = layers[d];
         await_root(tickets[d + 1], L.cTree);
         if (d + 1 == layers.size()) clock.mark_split("waiting for FRI roots (device busy)", waited_ms, "query plans while the device folds");
-        std::vector<uint64_t> positions = query_indexes(L.cTree.root, job.fri_query_count, L.column_length, (uint32_t)E);
-        std::vector<uint64_t> rows_wanted;
-        for (uint64_t p : positions) rows_wanted.push_back(p % (L.column_length / 4));
-        rows_wanted = unique_in_order(rows_wanted);
+        const Plan::Queries q = plan.layer_queries(L.cTree.root, L.column_length);
         Component &c = components[d];
         c.columnRoot = L.cTree.root;
-        rb.prove_batch(x, L.cTree, rows_wanted, &c.columnProof);
-        rb.gather_rows4(x, L.next.p, L.column_length / 4, rows_wanted, &c.columnProof);
-        rb.prove_batch(x, *L.pTree, positions, &c.polyProof);
-        rb.gather_rows4(x, L.column, L.rows, positions, &c.polyProof);
+        rb.prove_batch(x, L.cTree, q.rows, &c.columnProof);
+        rb.gather_rows4(x, L.next.p, L.column_length / 4, q.rows, &c.columnProof);
+        rb.prove_batch(x, *L.pTree, q.positions, &c.polyProof);
+        rb.gather_rows4(x, L.column, L.rows, q.positions, &c.polyProof);
     }
     if (layers.empty()) clock.mark_split("waiting for FRI roots (device busy)", waited_ms, "query plans while the device folds");
     clock.mark("last root here: the last layer's plan");
@@ -1172,15 +1249,8 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     }
     win.end();
     clock.mark("remainder + answers fetched (one sync)");
-    {
-        Bytes &raw = remainder_raw;
-        for (uint64_t i = 0; i < len; i++) remainder[i] = from16(raw.data() + ELEM * i);
-        // verifyRemainder (:223-252)
-        F rou = omega;
-        for (uint32_t d = 0; d < depth; d++) { rou = hf_mul(rou, rou); rou = hf_mul(rou, rou); }      // omega^(4^depth)
-        if (!remainder_is_low_degree(remainder, E, max_degree_plus1, rou, 1))
-            fail(GS_ERR_ARG, "Low degree proof failed: Remainder is not a valid degree %llu polynomial", (unsigned long long)(max_degree_plus1 - 1));
-    }
+    for (uint64_t i = 0; i < len; i++) remainder[i] = from16(remainder_raw.data() + ELEM * i);
+    check_remainder(plan, remainder, depth);
     clock.mark("remainder checked");
     clock.readme(x, "Computed low-degree proof: query answers + Computed %zu evaluation spot checks (one read-back), remainder verified", exe_positions.size());
     if (V > 1) {
@@ -1192,23 +1262,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     }
 
     clock.mark("query answers unpacked");
-    // ----- Serializer.serializeProof (:35-79)
-    out.clear();
-    out.insert(out.end(), eTree.root.begin(), eTree.root.end());
-    write_merkle_proof(out, evProof, (uint64_t)V * ELEM);
-    out.insert(out.end(), pTree0.root.begin(), pTree0.root.end());
-    write_merkle_proof(out, lcProof, 4 * ELEM);
-    if (components.size() > 255) fail(GS_ERR_ARG, "too many FRI components");
-    out.push_back((uint8_t)components.size());
-    for (auto &c : components) {
-        out.insert(out.end(), c.columnRoot.begin(), c.columnRoot.end());
-        write_merkle_proof(out, c.columnProof, 4 * ELEM);
-        write_merkle_proof(out, c.polyProof, 4 * ELEM);
-    }
-    if (remainder.size() > MAX_ARRAY) fail(GS_ERR_ARG, "remainder too long");
-    out.push_back(remainder.size() == MAX_ARRAY ? 0 : (uint8_t)remainder.size());
-    for (F v : remainder) { uint8_t b[ELEM]; le16(v, b); out.insert(out.end(), b, b + ELEM); }
-    write_input_shapes(out, input_shapes);
+    write_proof(out, eTree.root, evProof, V, pTree0.root, lcProof, components, remainder, input_shapes);
     clock.mark("serialized");
     clock.readme(x, "Proof serialized");
 }

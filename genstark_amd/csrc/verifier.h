@@ -164,16 +164,7 @@ bool merkle_check(int alg, const Bytes &root, const std::vector<uint64_t> &index
     return merkle_verify_batch(alg, root.data(), indexes, digests, mp.nodes, mp.depth);
 }
 
-// FiniteField.interpolate(xs, ys) for the handful of points of an assertion set / FiniteField.evalPolyAt, on host scalars
-std::vector<F> lagrange(const std::vector<F> &xs, const std::vector<F> &ys) {
-    const size_t n = xs.size();
-    Bytes xb(n * ELEM), yb(n * ELEM), cb(n * ELEM);
-    for (size_t i = 0; i < n; i++) { le16(xs[i], xb.data() + ELEM * i); le16(ys[i], yb.data() + ELEM * i); }
-    if (A.gs_small_interpolate(xb.data(), yb.data(), (uint32_t)n, cb.data())) fail(GS_ERR_ARG, "gs_small_interpolate failed");
-    std::vector<F> out(n);
-    for (size_t i = 0; i < n; i++) out[i] = from16(cb.data() + ELEM * i);
-    return out;
-}
+// FiniteField.evalPolyAt, on host scalars
 F horner(const std::vector<F> &poly, F x) {
     F r = 0;
     for (size_t k = poly.size(); k-- > 0;) r = hf_add(hf_mul(r, x), poly[k]);
@@ -213,11 +204,6 @@ void batch_invert(std::vector<F> &v) {
         v[i] = hf_mul(inv, pre[i]);
         inv = hf_mul(inv, vi);
     }
-}
-std::vector<uint64_t> augmented_rows(const std::vector<uint64_t> &positions, uint64_t column_length) {      // LowDegreeProver.ts:302-309
-    std::vector<uint64_t> out;
-    for (uint64_t p : positions) out.push_back(p % (column_length / 4));
-    return unique_in_order(out);
 }
 
 // the constraint evaluator of an AIR given as a register-machine program (kind 1), on host scalars: genstark_amd/air_generic.py
@@ -364,11 +350,8 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     if (T > (1ull << 32) / E) fail(GS_ERR_ARG, "a trace of %llu steps at extension factor %llu is beyond this verifier", (unsigned long long)T, (unsigned long long)E);
     const uint64_t N = T * E;
     const F omega = domain_root(job, N);
-    uint32_t max_degree = 1;
-    for (uint32_t i = 0; i < air.nconstraints; i++) max_degree = std::max(max_degree, air.degrees[i]);
-    uint64_t cf = 1;
-    while (cf < max_degree) cf <<= 1;
-    const uint64_t combination_degree = cf * T, composition_degree = std::max(combination_degree - T, T), b_inc = composition_degree - T;
+    const Plan plan = make_plan(job, T, E, omega);
+    const uint64_t combination_degree = plan.combination_degree, b_inc = plan.b_inc;
     // the number of FRI layers is a function of the domain size alone (LowDegreeProver.ts:179: fold while more than 256 values are
     // left); a proof with any other count is malformed — in particular one with extra layers, which would floor the degree bound of
     // the remainder to zero and leave the low-degree test with nothing to check
@@ -381,41 +364,16 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     }
 
     // ----- composition polynomial set-up (CompositionPolynomial.ts:29-69): the same coefficient stream as the prover's
-    struct RegData { uint32_t reg; std::vector<F> xs, ys, ipoly, zpoly; };
-    std::vector<RegData> rdata;
     for (uint32_t i = 0; i < job.nassertions; i++) {
         const gs_assertion &a = job.assertions[i];
         if (a.reg >= R) fail(GS_ERR_ARG, "Invalid assertion: register %u is outside of register bank", a.reg);
         if (a.step >= T) fail(GS_ERR_ARG, "Invalid assertion: step %llu is outside of execution trace", (unsigned long long)a.step);
-        RegData *d = nullptr;
-        for (auto &e : rdata) if (e.reg == a.reg) d = &e;
-        if (!d) { rdata.push_back(RegData{a.reg, {}, {}, {}, {}}); d = &rdata.back(); }
-        d->xs.push_back(hf_pow(omega, (hfe)(a.step * E)));
-        d->ys.push_back(from16(a.value));
     }
-    for (auto &d : rdata) {
-        d.ipoly = lagrange(d.xs, d.ys);                                    // BoundaryConstraints.ts:42
-        d.zpoly = {(F)1};
-        for (F x : d.xs) {                                                 // :24-30
-            std::vector<F> nz(d.zpoly.size() + 1, (F)0);
-            const F nx = hf_sub(0, x);
-            for (size_t k = 0; k < d.zpoly.size(); k++) { nz[k] = hf_add(nz[k], hf_mul(d.zpoly[k], nx)); nz[k + 1] = hf_add(nz[k + 1], d.zpoly[k]); }
-            d.zpoly.swap(nz);
-        }
-    }
-    const uint32_t bcount = (uint32_t)rdata.size();
-    std::vector<std::pair<uint64_t, std::vector<uint32_t>>> groups;
-    for (uint32_t i = 0; i < air.nconstraints; i++) {
-        const uint64_t d = (uint64_t)air.degrees[i] * T;
-        bool found = false;
-        for (auto &g : groups) if (g.first == d) { g.second.push_back(i); found = true; }
-        if (!found) groups.push_back({d, {i}});
-    }
-    uint32_t dcount = air.nconstraints;
-    for (auto &g : groups) if (g.first < combination_degree) dcount += (uint32_t)g.second.size();
-    const uint32_t bcoef = bcount * (composition_degree > T ? 2 : 1);
-    const uint32_t V = R + S, lccount = b_inc > 0 ? 2 * V : V;
-    const std::vector<F> coeffs = prng_many(evRoot, dcount + bcoef + lccount);       // d, then b, then the linear combination's (LinearCombination.ts:58-59)
+    const std::vector<Plan::Reg> &rdata = plan.regs;
+    std::vector<std::vector<F>> ipolys, zpolys;                            // per asserted register: BoundaryConstraints.ts:42, :24-30
+    for (auto &d : rdata) { ipolys.push_back(lagrange(d.xs, d.ys)); zpolys.push_back(plan.zero_poly(d)); }
+    const uint32_t bcount = (uint32_t)rdata.size(), dcount = plan.dcount, bcoef = plan.bcoef, V = R + S;
+    const std::vector<F> coeffs = plan.coefficients(evRoot, V);
     const F x_last = hf_pow(omega, (hfe)((T - 1) * E));
 
     // static registers of the AIR at a point (kind 1: K_s(x^(T/period)); kind 0: the round-constant register)
@@ -503,11 +461,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     };
 
     // ----- spot-check positions and the evaluation tree (lib/Stark.ts:183-216)
-    const uint32_t exe_count = (uint32_t)std::min<uint64_t>(job.exe_query_count, N - N / E);
-    const std::vector<uint64_t> positions = query_indexes(lcRoot, exe_count, N, (uint32_t)E);
-    std::vector<uint64_t> aug;
-    for (uint64_t p : positions) { aug.push_back(p); aug.push_back((p + E) % N); }
-    aug = unique_in_order(aug);
+    const std::vector<uint64_t> positions = plan.exe_positions(lcRoot), aug = plan.evaluation_positions(positions);
     if (evProof.values.size() != aug.size()) fail(GS_ERR_ARG, "malformed proof: the evaluation proof does not hold one leaf per queried position");
     std::map<uint64_t, size_t> at_leaf;
     for (size_t i = 0; i < aug.size(); i++) at_leaf[aug[i]] = i;
@@ -527,7 +481,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         const F x = hf_pow(omega, (hfe)step);
         xsq.push_back(x);
         dens.push_back(hf_sub(hf_pow(x, (hfe)T), 1));                                                  // ZeroPolynomial.ts:28-34: Z = (x^T - 1) / (x - x_last)
-        for (auto &d : rdata) dens.push_back(horner(d.zpoly, x));                                      // BoundaryConstraints.ts:55-69
+        for (auto &zp : zpolys) dens.push_back(horner(zp, x));                                      // BoundaryConstraints.ts:55-69
     }
     batch_invert(dens);
     for (size_t k = 0; k < static_polys.size(); k++) {                        // K_s(x^(T/period)) at every queried x
@@ -544,7 +498,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         leaf_values((step + E) % N, n, unused);
         std::vector<F> q = constraints_at(pi, p, n, s);
         if (q.size() != air.nconstraints) fail(GS_ERR_ARG, "constraint evaluator returned the wrong number of values");
-        for (auto &g : groups) {
+        for (auto &g : plan.groups) {
             if (g.first == combination_degree) continue;
             const F power = hf_pow(x, (hfe)(combination_degree - g.first));
             for (uint32_t i : g.second) q.push_back(hf_mul(q[i], power));
@@ -553,7 +507,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         for (size_t k = 0; k < q.size(); k++) qc = hf_add(qc, hf_mul(q[k], coeffs[k]));
         const F dValue = hf_mul(hf_mul(qc, hf_sub(x, x_last)), dens[di++]);                             // Q / Z = Q (x - x_last) / (x^T - 1)
         std::vector<F> b;
-        for (auto &d : rdata) b.push_back(hf_mul(hf_sub(p[d.reg], horner(d.ipoly, x)), dens[di++]));
+        for (uint32_t r = 0; r < bcount; r++) b.push_back(hf_mul(hf_sub(p[rdata[r].reg], horner(ipolys[r], x)), dens[di++]));
         const F xb = hf_pow(x, (hfe)b_inc);
         if (b_inc > 0) for (uint32_t i = 0; i < bcount; i++) b.push_back(hf_mul(b[i], xb));
         F bValue = 0;
@@ -590,7 +544,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     }
     Bytes pRoot = lcRoot;
     F rou = omega;
-    uint64_t max_degree_plus1 = composition_degree;
+    uint64_t max_degree_plus1 = plan.composition_degree;
     column_length /= 4;
     const F zeta[4] = {(F)1, hf_pow(omega, (hfe)(N / 4)), hf_pow(omega, (hfe)(N / 2)), hf_pow(omega, (hfe)(N / 4 * 3))};      // :75-77
     const F inv4 = hf_inv((F)4);
@@ -598,8 +552,8 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     for (uint32_t depth = 0; depth < ncomp; depth++) {
         Comp &c = comps[depth];
         if (column_length < 4) fail(GS_ERR_ARG, "malformed proof: too many FRI components");
-        const std::vector<uint64_t> pos = query_indexes(c.columnRoot, job.fri_query_count, column_length, (uint32_t)E);
-        const std::vector<uint64_t> rows = augmented_rows(pos, column_length);
+        const Plan::Queries q = plan.layer_queries(c.columnRoot, column_length);
+        const std::vector<uint64_t> &pos = q.positions, &rows = q.rows;
         if (c.columnProof.values.size() != rows.size() || c.polyProof.values.size() != pos.size()) fail(GS_ERR_ARG, "malformed proof: wrong number of rows at depth %u", depth);
         const std::vector<F> col = column_values(c.columnProof, pos, rows, column_length);
         if (!merkle_check(alg, c.columnRoot, rows, c.columnProof)) fail(GS_ERR_ARG, "Verification of column Merkle proof failed at depth %u", depth);
@@ -664,16 +618,10 @@ extern "C" {
 
 static int verify_entry(const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap) {
     if (!job || !proof) return GS_ERR_ARG;
-    try {
+    return guarded(err, errcap, GS_ERR_ARG, [&]() -> int {
         verify_impl(*job, proof, len);
         return GS_OK;
-    } catch (const Fail &f) {
-        if (err && errcap) snprintf(err, (size_t)errcap, "%s", f.msg.c_str());
-        return f.code ? f.code : GS_ERR_ARG;
-    } catch (const std::exception &e) {
-        if (err && errcap) snprintf(err, (size_t)errcap, "%s", e.what());
-        return GS_ERR_ARG;
-    }
+    });
 }
 int gs_prover_verify(const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap) {
     if (!g_bound) return GS_ERR_UNSUPPORTED;
