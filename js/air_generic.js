@@ -7,7 +7,7 @@
 // the transition / constraint / init programs in the {op, dst, a, b} encoding of include/gstark.h.  The device interprets the
 // programs (gs_air_trace, gs_air_trace_segments, gs_air_constraints through the N-API shim); the verifier side interprets the
 // constraint program on BigInt.
-const { Matrix, Vector, native, le, packLe } = require('./galois');
+const { Matrix, Vector } = require('./galois');
 
 const OP = { LOADC: 0, LOADR: 1, LOADN: 2, LOADS: 3, ADD: 4, SUB: 5, MUL: 6, POW: 7, POWC: 8, OUT: 9 };
 
@@ -23,7 +23,7 @@ class Program {
             if (!(op >= 0 && op <= OP.OUT)) throw new TypeError(`program: unknown opcode ${op}`);
         }
     }
-    constsBuffer() { return this.consts.length ? packLe(this.consts) : le(0n); }
+    constsBuffer(field) { return this.consts.length ? field.packLe(this.consts) : field.le(0n); }
     run(field, cur, next, statics) {   // host interpreter, as Program.run of genstark_amd/air_generic.py
         const vm = new Array(this.nregs).fill(0n), out = new Array(this.nout).fill(0n), c = this.code;
         for (let i = 0; i < c.length; i += 4) {
@@ -88,10 +88,10 @@ class ProvingContext extends Context {
             const m = col.length;
             const g = f.exp(this.rootOfUnity, BigInt(this.extensionFactor * (this.traceLength / m)));
             const values = new Vector(f, m);
-            native().call('gs_upload', f.ctx, values.ptr, packed, packed.length);
+            f.lib.call('gs_upload', f.ctx, values.ptr, packed, packed.length);
             return f.interpolateRoots(f.getPowerSeries(g, m), values);
         };
-        this.packedSecret = this.secretColumns.map(col => packLe(col));
+        this.packedSecret = this.secretColumns.map(col => f.packLe(col));
         const secretPolys = this.secretColumns.map((col, s) => {
             const m = col.length;
             if (!isPow2(m) || this.traceLength % m) throw new Error('a secret register column must be a power of 2 long and divide the trace length');
@@ -111,7 +111,7 @@ class ProvingContext extends Context {
             const wk = f.exp(this.compositionDomain.seriesBase, BigInt(this.traceLength / m));
             return { ln, tab: f.evalPolyAtRoots(poly, f.getPowerSeries(wk, ln)) };
         };
-        if (!air._packedStatic) air._packedStatic = air.staticRegisters.map(v => packLe(v));
+        if (!air._packedStatic) air._packedStatic = air.staticRegisters.map(v => f.packLe(v));
         if (!air._publicTables) air._publicTables = air.staticRegisters.map((values, s) => table(values.length, columnPoly(values, air._packedStatic[s])));
         const all = air._publicTables.concat(secretPolys.map((poly, s) => table(this.secretColumns[s].length, poly)));
         this.staticLens = all.map(e => e.ln);
@@ -120,28 +120,28 @@ class ProvingContext extends Context {
         this.staticTables = new Vector(f, Math.max(total, 1));
         let off = 0;
         all.forEach(e => {
-            native().call('gs_copy', f.ctx, this.staticTables.ptr + BigInt(off * f.elementSize), e.tab.ptr, e.ln * f.elementSize);
+            f.lib.call('gs_copy', f.ctx, this.staticTables.ptr + BigInt(off * f.elementSize), e.tab.ptr, e.ln * f.elementSize);
             off += e.ln;
         });
         if (!secretPolys.length) { air._tableBlock = this.staticTables; air._tableLens = this.staticLens; }
     }
     allStaticColumns() { return this.air.staticRegisters.concat(this.secretColumns); }
     staticValuesPacked() {
-        const parts = (this.air._packedStatic || this.air.staticRegisters.map(v => packLe(v))).concat(this.packedSecret);
-        return parts.length ? Buffer.concat(parts) : le(0n);
+        const f = this.field, parts = (this.air._packedStatic || this.air.staticRegisters.map(v => f.packLe(v))).concat(this.packedSecret);
+        return parts.length ? Buffer.concat(parts) : f.le(0n);
     }
     generateExecutionTrace() {   // lib/Stark.ts:97
         const air = this.air, f = this.field, t = air.transitionProgram;
         const m = new Matrix(f, air.traceRegisterCount, this.traceLength);
         const periods = this.allStaticColumns().map(v => v.length);
-        const first = this.firstRows.packedFirstRows || Buffer.concat(this.firstRows.map(row => packLe(row)));
+        const first = this.firstRows.packedFirstRows || Buffer.concat(this.firstRows.map(row => f.packLe(row)));
         const nrows = this.firstRows.packedFirstRows ? this.firstRows.rows : this.firstRows.length;
         if (air.segmentLength === null) {
-            native().call('gs_air_trace', f.ctx, t.code, t.ninstr, t.constsBuffer(), t.consts.length, t.nregs, air.traceRegisterCount,
+            f.lib.call('gs_air_trace', f.ctx, t.code, t.ninstr, t.constsBuffer(f), t.consts.length, t.nregs, air.traceRegisterCount,
                 this.staticValuesPacked(), periods, periods.length, first, this.traceLength, m.ptr);
         } else {
             const init = air.initProgram;
-            native().call('gs_air_trace_segments', f.ctx, t.code, t.ninstr, init ? init.code : [], init ? init.ninstr : 0, t.constsBuffer(), t.consts.length,
+            f.lib.call('gs_air_trace_segments', f.ctx, t.code, t.ninstr, init ? init.code : [], init ? init.ninstr : 0, t.constsBuffer(f), t.consts.length,
                 t.nregs, air.traceRegisterCount, this.staticValuesPacked(), periods, periods.length, first, nrows, air.segmentLength, m.ptr);
         }
         return m;
@@ -154,7 +154,7 @@ class ProvingContext extends Context {
         const air = this.air, f = this.field, e = air.evaluationProgram, nc = this.compositionDomain.length;
         const pComp = f.evalPolysAtRoots(pPolys, this.compositionDomain);
         const q = new Matrix(f, air.constraintDegrees.length, nc);
-        native().call('gs_air_constraints', f.ctx, e.code, e.ninstr, e.constsBuffer(), e.consts.length, e.nregs, air.traceRegisterCount,
+        f.lib.call('gs_air_constraints', f.ctx, e.code, e.ninstr, e.constsBuffer(f), e.consts.length, e.nregs, air.traceRegisterCount,
             air.constraintDegrees.length, pComp.ptr, nc, nc / this.traceLength, this.staticTables.ptr, this.staticLens, this.staticLens.length, q.ptr);
         return q;
     }
@@ -204,7 +204,7 @@ class GenericAir {
         this.rootOfUnity = field.getRootOfUnity(this.steps * ef);
     }
     /** the statement's first rows already in the driver's wire form, for many proofs of one seed (js/prover.js: packSeed) */
-    packSeed(seed) { const rows = this.firstRows(seed); const flat = []; for (const row of rows) for (const v of row) flat.push(v); return { packedFirstRows: packLe(flat), rows: rows.length }; }
+    packSeed(seed) { const rows = this.firstRows(seed); const flat = []; for (const row of rows) for (const v of row) flat.push(v); return { packedFirstRows: this.field.packLe(flat), rows: rows.length }; }
     firstRows(seed) {
         if (this.fixedFirstRows) return this.fixedFirstRows;
         if (seed && seed.packedFirstRows) return seed;            // a packed seed: nothing to lay out
@@ -227,7 +227,7 @@ class GenericAir {
         const air = this;
         return { air, firstRows: this.firstRows(seed), staticTables: this._tableBlock, staticLens: this._tableLens, secretRegisterTraces: [],
                  allStaticColumns() { return air.staticRegisters; },
-                 staticValuesPacked() { return air._packedStatic.length ? Buffer.concat(air._packedStatic) : le(0n); } };
+                 staticValuesPacked() { return air._packedStatic.length ? Buffer.concat(air._packedStatic) : air.field.le(0n); } };
     }
     /** a proving context from first rows and secret columns that are already reduced field elements (the loader's plan: js/air_assembly.js) */
     contextFor(firstRows, secretColumns) { return new ProvingContext(this, firstRows, secretColumns || []); }

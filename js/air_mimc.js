@@ -3,7 +3,7 @@
 // lib/Stark.ts and lib/components/*.ts consume, instantiated for the MiMC AIR of examples/mimc/mimc128Assembly.ts:28-51
 // (JS twin of genstark_amd/air.py; the AirAssembly compiler itself is out of scope).
 const crypto = require('crypto');
-const { createPrimeField, MODULUS, Matrix, native, le } = require('./galois');
+const { createPrimeField, MODULUS, Matrix } = require('./galois');
 
 function sha256Prng(seed, count, field) {  // UNVERIFIED restatement of air-assembly prng.sha256 (see genstark_amd/air.py)
     const out = [];
@@ -55,7 +55,7 @@ class ProvingContext extends Context {
     }
     generateExecutionTrace() {
         const f = this.field, m = new Matrix(f, 1, this.traceLength), rc = this.air.roundConstants;
-        native().call('gs_mimc_trace', f.ctx, le(this.seed), Buffer.concat(rc.map(le)), rc.length, this.traceLength, m.ptr);
+        f.lib.call('gs_mimc_trace', f.ctx, f.le(this.seed), f.packLe(rc), rc.length, this.traceLength, m.ptr);
         return m;
     }
     generateStaticTrace() {
@@ -67,7 +67,7 @@ class ProvingContext extends Context {
         const f = this.field, nc = this.compositionDomain.length;
         const pComp = f.evalPolysAtRoots(pPolys, this.compositionDomain);
         const q = new Matrix(f, 1, nc);
-        native().call('gs_mimc_constraints', f.ctx, pComp.ptr, nc, nc / this.traceLength, this.kTable.ptr, this.kTable.length, q.ptr);
+        f.lib.call('gs_mimc_constraints', f.ctx, pComp.ptr, nc, nc / this.traceLength, this.kTable.ptr, this.kTable.length, q.ptr);
         return q;
     }
 }

@@ -7,76 +7,143 @@ const crypto = require('crypto');
 const path = require('path');
 
 const MODULUS = 2n ** 128n - 9n * 2n ** 32n + 1n;
-// one build flavour of the library per field (genstark_amd/csrc/build.sh); a process works in ONE field, like the reference's
-// example scripts: the first createPrimeField(modulus) picks the library, ELEMENT_SIZE / LOADED_MODULUS follow from it
+// one build flavour of the library per field (genstark_amd/csrc/build.sh).  A process may work in several fields: each modulus resolves
+// to its library, which is opened once (the addon's open(): a library object with its own contexts and driver bindings) and shared by
+// every PrimeField of that modulus
 const LIBRARIES = new Map([
     [MODULUS, 'libgstark_hip.so'],
     [2n ** 64n - 21n * 2n ** 30n + 1n, 'libgstark_hip_q64.so'], [2n ** 32n - 3n * 2n ** 25n + 1n, 'libgstark_hip_q32.so'], [96769n, 'libgstark_hip_q17.so'],
     [2n ** 256n - 351n * 2n ** 32n + 1n, 'libgstark_hip_p256.so'], [2n ** 224n - 2n ** 96n + 1n, 'libgstark_hip_p224.so'],
 ]);
-let ELEMENT_SIZE = 16;
-let LOADED_MODULUS = null;
+const RUNTIME_LIBRARY = 'libgstark_hip_rt.so';
 
-let addon = null;
-function native(modulus) {
-    if (!addon) {
-        const wanted = modulus === undefined ? MODULUS : BigInt(modulus);
-        // a modulus none of the fixed builds knows: the runtime-modulus build (gs_set_modulus: any odd modulus below 2^256, once per process)
-        const runtime = !process.env.GSTARK_LIB && !LIBRARIES.has(wanted);
-        if (runtime && (wanted < 3n || wanted % 2n === 0n || wanted >> 256n)) throw new TypeError(`no build of the library for the field of ${wanted} elements`);
-        const lib = process.env.GSTARK_LIB || path.join(__dirname, '..', 'genstark_amd', 'csrc', runtime ? 'libgstark_hip_rt.so' : LIBRARIES.get(wanted));
-        const a = require(process.env.GSTARK_ADDON || path.join(__dirname, '..', 'napi', 'gstark_napi.node'));      // GSTARK_ADDON: an instrumented build (tools/build_sanitized.sh)
-        const name = a.load(lib);
-        if (name !== 'hip-gfx950' && process.env.GSTARK_ALLOW_TEST_DOUBLE !== '1') {
-            throw new Error(`refusing backend ${name}: the product path runs on hip-gfx950 only (no CPU fallback)`);
+// deterministic Miller-Rabin (the first 24 primes as bases: a proof of primality below 3.3e24, a strong probable-prime test above)
+const MR_BASES = [2n, 3n, 5n, 7n, 11n, 13n, 17n, 19n, 23n, 29n, 31n, 37n, 41n, 43n, 47n, 53n, 59n, 61n, 67n, 71n, 73n, 79n, 83n, 89n];
+function powMod(b, e, m) { let r = 1n; b %= m; while (e > 0n) { if (e & 1n) r = r * b % m; b = b * b % m; e >>= 1n; } return r; }
+function isProbablePrime(n) {
+    if (n < 2n) return false;
+    for (const p of MR_BASES) { if (n === p) return true; if (n % p === 0n) return false; }
+    let d = n - 1n, s = 0;
+    while (!(d & 1n)) { d >>= 1n; s++; }
+    for (const a of MR_BASES) {
+        let x = powMod(a, d, n);
+        if (x === 1n || x === n - 1n) continue;
+        let i = 1;
+        for (; i < s; i++) { x = x * x % n; if (x === n - 1n) break; }
+        if (i === s) return false;
+    }
+    return true;
+}
+
+let addonModule = null;
+function addon() {      // GSTARK_ADDON: an instrumented build (tools/build_sanitized.sh)
+    if (!addonModule) addonModule = require(process.env.GSTARK_ADDON || path.join(__dirname, '..', 'napi', 'gstark_napi.node'));
+    return addonModule;
+}
+const OPENED = new Map();        // library path -> { lib, modulus, elementSize }
+const BY_MODULUS = new Map();    // modulus -> the same record
+let runtimeModulus = null;       // the runtime-modulus library's field (its constants are per process: one such modulus per process)
+let firstLib = null;             // the default field's library: the first one opened
+
+function openLibrary(file, setModulus, wanted) {
+    let rec = OPENED.get(file);
+    if (!rec) {
+        const lib = addon().open(file);
+        if (lib.backend !== 'hip-gfx950' && process.env.GSTARK_ALLOW_TEST_DOUBLE !== '1') {
+            throw new Error(`refusing backend ${lib.backend}: the product path runs on hip-gfx950 only (no CPU fallback)`);
         }
-        if (runtime || process.env.GSTARK_SET_MODULUS === '1') {      // (GSTARK_SET_MODULUS=1: GSTARK_LIB names a runtime-modulus library — the tests' double)
+        if (setModulus) {
             const bytes = Buffer.alloc(32);
             let x = wanted;
             for (let i = 0; i < 32; i++) { bytes[i] = Number(x & 0xFFn); x >>= 8n; }
-            a.call('gs_set_modulus', bytes, 32);
+            lib.call('gs_set_modulus', bytes, 32);
         }
-        const info = a.fieldInfo();
-        ELEMENT_SIZE = info.elementSize;
-        LOADED_MODULUS = fromLe(info.modulus, 0, info.elementSize);
-        addon = a;
+        const info = lib.fieldInfo();
+        rec = { lib, elementSize: info.elementSize, modulus: fromLe(info.modulus, 0, info.elementSize) };
+        OPENED.set(file, rec);
+        if (!firstLib) firstLib = rec;
     }
-    return addon;
+    return rec;
 }
 
-// bigint <-> little-endian bytes (lib/utils/serialization.ts:140-146 layout), a 64-bit word at a time: a column of an input register is
-// 10^4..10^5 of these per proof, and a byte at a time they cost more than the proof (element sizes are 16 or 32 bytes)
-const M64 = (1n << 64n) - 1n;
-function putLe(b, off, v) {
-    let x = BigInt(v);
-    for (let i = 0; i < ELEMENT_SIZE; i += 8) { b.writeBigUInt64LE(x & M64, off + i); x >>= 64n; }
+/** modulus -> { lib, modulus, elementSize }: the library computing in that field, opened on first use */
+function libraryFor(modulus) {
+    const wanted = modulus === undefined ? (firstLib ? firstLib.modulus : MODULUS) : BigInt(modulus);
+    const known = BY_MODULUS.get(wanted);
+    if (known) return known;
+    let rec;
+    if (process.env.GSTARK_LIB) {
+        // one library named for every field (an instrumented or test build): it computes in one field, a second modulus is refused
+        // (GSTARK_SET_MODULUS=1: GSTARK_LIB names a runtime-modulus library — the tests' double)
+        const setModulus = process.env.GSTARK_SET_MODULUS === '1';
+        if (setModulus && !OPENED.has(process.env.GSTARK_LIB)) checkRuntimeModulus(wanted);
+        rec = openLibrary(process.env.GSTARK_LIB, setModulus, wanted);
+        if (wanted !== rec.modulus) throw new TypeError(`the loaded library computes in the field of ${rec.modulus} elements, not ${wanted} (one field per process)`);
+    } else {
+        // a modulus none of the fixed builds knows: the runtime-modulus build (gs_set_modulus: any odd prime below 2^256, once per process)
+        const runtime = !LIBRARIES.has(wanted);
+        if (runtime) {
+            checkRuntimeModulus(wanted);
+            if (runtimeModulus !== null && runtimeModulus !== wanted) {
+                throw new TypeError(`the runtime-modulus library already computes in the field of ${runtimeModulus} elements; it cannot also take ${wanted} (one runtime modulus per process)`);
+            }
+        }
+        const name = runtime ? RUNTIME_LIBRARY : LIBRARIES.get(wanted);
+        // GSTARK_LIB_DIR (tests): every flavour from one directory under the CPU oracle's file names (oracle/Makefile: liboracle*.so)
+        const file = process.env.GSTARK_LIB_DIR ? path.join(process.env.GSTARK_LIB_DIR, name.replace('libgstark_hip', 'liboracle'))
+                                               : path.join(__dirname, '..', 'genstark_amd', 'csrc', name);
+        rec = openLibrary(file, runtime, wanted);
+        if (runtime) runtimeModulus = wanted;
+        if (wanted !== rec.modulus) throw new TypeError(`the library ${file} computes in the field of ${rec.modulus} elements, not ${wanted}`);
+    }
+    BY_MODULUS.set(wanted, rec);
+    return rec;
 }
-function le(v) {  // bigint -> elementSize-byte little-endian Buffer
-    const b = Buffer.allocUnsafe(ELEMENT_SIZE);
-    putLe(b, 0, v);
+function checkRuntimeModulus(q) {
+    if (q < 3n || q % 2n === 0n || q >> 256n) throw new TypeError(`no build of the library for the field of ${q} elements`);
+    if (!isProbablePrime(q)) throw new TypeError(`${q} is not prime: no field of ${q} elements`);
+}
+
+/** the library object of a field (the default field's when no modulus is given): its members are the addon's, on that library */
+function native(modulus) { return libraryFor(modulus).lib; }
+
+// bigint <-> little-endian bytes (lib/utils/serialization.ts:140-146 layout), a 64-bit word at a time: a column of an input register is
+// 10^4..10^5 of these per proof, and a byte at a time they cost more than the proof (element sizes are 16 or 32 bytes).  The module-level
+// helpers take the element size of a field given as their last argument, else of the default field; PrimeField has the same members.
+const M64 = (1n << 64n) - 1n;
+const sizeOf = field => (field && typeof field === 'object' && field.elementSize) ? field.elementSize : (firstLib ? firstLib.elementSize : 16);
+function putLe(b, off, v, size) {
+    let x = BigInt(v);
+    for (let i = 0; i < size; i += 8) { b.writeBigUInt64LE(x & M64, off + i); x >>= 64n; }
+}
+function le(v, field) {  // bigint -> elementSize-byte little-endian Buffer
+    const size = sizeOf(field);
+    const b = Buffer.allocUnsafe(size);
+    putLe(b, 0, v, size);
     return b;
 }
 /** values (BigInt, already reduced; or anything BigInt() takes when `mod` is given) -> ONE Buffer of their little-endian elements */
-function packLe(values, mod) {
+function packLe(values, mod, field) {
+    const size = sizeOf(field);
     if (mod) { const reduced = new Array(values.length); for (let i = 0; i < values.length; i++) reduced[i] = mod(BigInt(values[i])); values = reduced; }
     // the addon copies the BigInts' words (napi_get_value_bigint_words: ~30 ns per element); without it — or for the handful of values
     // most calls carry — the loop below
-    if (values.length >= 64 && addon && addon.packElements) return addon.packElements(values, ELEMENT_SIZE);
-    const b = Buffer.allocUnsafe(values.length * ELEMENT_SIZE);
-    for (let i = 0; i < values.length; i++) putLe(b, i * ELEMENT_SIZE, values[i]);
+    if (values.length >= 64 && addonModule && addonModule.packElements) return addonModule.packElements(values, size);
+    const b = Buffer.allocUnsafe(values.length * size);
+    for (let i = 0; i < values.length; i++) putLe(b, i * size, values[i], size);
     return b;
 }
 /** a Buffer of little-endian elements -> BigInt[] */
 function unpackLe(raw, size) {
-    if (size === undefined) size = ELEMENT_SIZE;
+    if (size === undefined) size = sizeOf();
     const n = raw.length / size;
-    if (n >= 64 && (size === 16 || size === 32) && addon && addon.unpackElements) return addon.unpackElements(raw, size);
+    if (n >= 64 && (size === 16 || size === 32) && addonModule && addonModule.unpackElements) return addonModule.unpackElements(raw, size);
     const out = new Array(n);
     for (let i = 0; i < n; i++) out[i] = fromLe(raw, i * size, size);
     return out;
 }
 function fromLe(buf, off = 0, size) {
-    if (size === undefined) size = ELEMENT_SIZE;
+    if (size === undefined) size = sizeOf();
     let v = 0n;
     if (size % 8 === 0) { for (let i = size - 8; i >= 0; i -= 8) v = (v << 64n) | buf.readBigUInt64LE(off + i); return v; }
     for (let i = size - 1; i >= 0; i--) v = (v << 8n) | BigInt(buf[off + i]);
@@ -88,20 +155,20 @@ function sha256(value) {  // same helper as lib/components/QueryIndexGenerator.t
 }
 
 const registry = (typeof FinalizationRegistry !== 'undefined')
-    ? new FinalizationRegistry(({ ctx, ptr }) => { try { native().call('gs_free', ctx, ptr); } catch (e) { /* context gone */ } })
+    ? new FinalizationRegistry(({ lib, ctx, ptr }) => { try { lib.call('gs_free', ctx, ptr); } catch (e) { /* context gone */ } })
     : null;
 
 class DeviceBuffer {
     constructor(field, bytes) {
         this.field = field;
-        this.ptr = native().alloc(field.ctx, bytes > 16 ? bytes : 16);
-        if (registry) registry.register(this, { ctx: field.ctx, ptr: this.ptr });
+        this.ptr = field.lib.alloc(field.ctx, bytes > 16 ? bytes : 16);
+        if (registry) registry.register(this, { lib: field.lib, ctx: field.ctx, ptr: this.ptr });
     }
 }
 
 class Vector {
     constructor(field, length, owner, offset = 0n, elementSize) {
-        if (elementSize === undefined) elementSize = ELEMENT_SIZE;
+        if (elementSize === undefined) elementSize = field.elementSize;
         this.field = field; this.length = length; this.elementSize = elementSize;
         this.owner = owner || new DeviceBuffer(field, length * elementSize);
         this.offset = offset;
@@ -112,7 +179,7 @@ class Vector {
     toBuffer(start = 0, count) {
         count = (count === undefined) ? this.length - start : count;
         const out = Buffer.alloc(count * this.elementSize);
-        if (count) native().call('gs_download', this.field.ctx, out, this.ptr + BigInt(start * this.elementSize), out.length);
+        if (count) this.field.lib.call('gs_download', this.field.ctx, out, this.ptr + BigInt(start * this.elementSize), out.length);
         return out;
     }
     getValue(index) { return fromLe(this.toBuffer(index, 1), 0, this.elementSize); }
@@ -123,50 +190,61 @@ class Vector {
     }
     valuesAt(indexes) {
         const out = Buffer.alloc(indexes.length * this.elementSize);
-        if (indexes.length) native().call('gs_gather', this.field.ctx, this.ptr, this.elementSize, indexes, indexes.length, out);
+        if (indexes.length) this.field.lib.call('gs_gather', this.field.ctx, this.ptr, this.elementSize, indexes, indexes.length, out);
         return indexes.map((_, i) => out.slice(i * this.elementSize, (i + 1) * this.elementSize));
     }
 }
 
 class Matrix {
     constructor(field, rowCount, colCount, owner, offset = 0n) {
-        this.field = field; this.rowCount = rowCount; this.colCount = colCount; this.elementSize = ELEMENT_SIZE;
-        this.owner = owner || new DeviceBuffer(field, rowCount * colCount * ELEMENT_SIZE);
+        const es = field.elementSize;
+        this.field = field; this.rowCount = rowCount; this.colCount = colCount; this.elementSize = es;
+        this.owner = owner || new DeviceBuffer(field, rowCount * colCount * es);
         this.offset = offset;
         this.quarticDomain = undefined;
     }
     get ptr() { return this.owner.ptr + this.offset; }
     toBuffer() {
-        const out = Buffer.alloc(this.rowCount * this.colCount * ELEMENT_SIZE);
-        if (out.length) native().call('gs_download', this.field.ctx, out, this.ptr, out.length);
+        const out = Buffer.alloc(this.rowCount * this.colCount * this.elementSize);
+        if (out.length) this.field.lib.call('gs_download', this.field.ctx, out, this.ptr, out.length);
         return out;
     }
     getValue(row, col) {
-        const out = Buffer.alloc(ELEMENT_SIZE);
-        native().call('gs_download', this.field.ctx, out, this.ptr + BigInt((row * this.colCount + col) * ELEMENT_SIZE), ELEMENT_SIZE);
-        return fromLe(out);
+        const es = this.elementSize, out = Buffer.alloc(es);
+        this.field.lib.call('gs_download', this.field.ctx, out, this.ptr + BigInt((row * this.colCount + col) * es), es);
+        return fromLe(out, 0, es);
     }
     toValues() {
-        const flat = unpackLe(this.toBuffer(), ELEMENT_SIZE), out = [];
+        const flat = unpackLe(this.toBuffer(), this.elementSize), out = [];
         for (let r = 0; r < this.rowCount; r++) out.push(flat.slice(r * this.colCount, (r + 1) * this.colCount));
         return out;
     }
     rowsToBuffers(indexes) {  // lib/components/LowDegreeProver.ts:53,214,217
-        const rec = this.colCount * ELEMENT_SIZE;
+        const rec = this.colCount * this.elementSize;
         const out = Buffer.alloc(indexes.length * rec);
-        if (indexes.length) native().call('gs_gather', this.field.ctx, this.ptr, rec, indexes, indexes.length, out);
+        if (indexes.length) this.field.lib.call('gs_gather', this.field.ctx, this.ptr, rec, indexes, indexes.length, out);
         return indexes.map((_, i) => out.slice(i * rec, (i + 1) * rec));
     }
-    row(r) { return new Vector(this.field, this.colCount, this.owner, this.offset + BigInt(r * this.colCount * ELEMENT_SIZE)); }
+    row(r) { return new Vector(this.field, this.colCount, this.owner, this.offset + BigInt(r * this.colCount * this.elementSize)); }
 }
 
 class PrimeField {
     constructor(modulus, options) {
-        native(modulus);
-        if (BigInt(modulus) !== LOADED_MODULUS) throw new TypeError(`the loaded library computes in the field of ${LOADED_MODULUS} elements, not ${modulus} (one field per process)`);
-        this.modulus = LOADED_MODULUS; this.elementSize = ELEMENT_SIZE; this.isOptimized = true;
+        const rec = libraryFor(modulus);
+        this.lib = rec.lib; this.modulus = rec.modulus; this.elementSize = rec.elementSize; this.isOptimized = true;
         this.zero = 0n; this.one = 1n;
-        this.ctx = (options && options.ctx) || native().ctxCreate((options && options.device) || 0);
+        this.ctx = (options && options.ctx) || this.lib.ctxCreate((options && options.device) || 0);
+    }
+    // ---- this field's element bytes (the module-level le / packLe / unpackLe / fromLe with this field's element size)
+    le(v) { return le(v, this); }
+    packLe(values, mod) { return packLe(values, mod, this); }
+    unpackLe(raw) { return unpackLe(raw, this.elementSize); }
+    fromLe(buf, off = 0) { return fromLe(buf, off, this.elementSize); }
+    /** every Vector / Matrix an operation takes must live in this field's library: a gs_ctx or a pointer of another never reaches it */
+    _own(...xs) {
+        for (const x of xs) {
+            if (x && x.field && x.field.lib !== this.lib) throw new TypeError(`a vector or matrix of the field of ${x.field.modulus} elements was passed to the field of ${this.modulus} elements`);
+        }
     }
     // ---- scalars
     mod(v) { return v >= 0n ? v % this.modulus : ((v % this.modulus) + this.modulus) % this.modulus; }
@@ -190,6 +268,7 @@ class PrimeField {
     }
     getRootOfUnity(order) {  // UNVERIFIED restatement (SURVEY appendix A.3)
         const o = BigInt(order);
+        if (o < 1n || (this.modulus - 1n) % o !== 0n) throw new Error(`the field of ${this.modulus} elements has no root of unity of order ${order}: it does not divide p - 1`);
         for (let i = 2n; i < 65536n; i++) {
             const g = this.exp(i, (this.modulus - 1n) / o);
             if (this.exp(g, o) === 1n && (o === 1n || this.exp(g, o / 2n) !== 1n)) return g;
@@ -200,7 +279,7 @@ class PrimeField {
     newVector(length) { return new Vector(this, length); }
     newVectorFrom(values) {
         const v = new Vector(this, values.length);
-        if (values.length) native().call('gs_upload', this.ctx, v.ptr, packLe(values, x => this.mod(x)), values.length * ELEMENT_SIZE);
+        if (values.length) this.lib.call('gs_upload', this.ctx, v.ptr, this.packLe(values, x => this.mod(x)), values.length * this.elementSize);
         return v;
     }
     newMatrix(rows, cols) { return new Matrix(this, rows, cols); }
@@ -210,27 +289,29 @@ class PrimeField {
         if (rows * cols) {
             const flat = new Array(rows * cols);
             for (let r = 0; r < rows; r++) for (let c = 0; c < cols; c++) flat[r * cols + c] = values[r][c];
-            native().call('gs_upload', this.ctx, m.ptr, packLe(flat, x => this.mod(x)), rows * cols * ELEMENT_SIZE);
+            this.lib.call('gs_upload', this.ctx, m.ptr, this.packLe(flat, x => this.mod(x)), rows * cols * this.elementSize);
         }
         return m;
     }
     newMatrixFromVectors(vectors) {
+        this._own(...vectors);
         // shorter rows are zero-extended (polynomials of different degrees: BoundaryConstraints.ts:84-85)
         const cols = Math.max(...vectors.map(v => v.length)); const m = new Matrix(this, vectors.length, cols);
         vectors.forEach((v, r) => {
-            native().call('gs_copy', this.ctx, m.ptr + BigInt(r * cols * ELEMENT_SIZE), v.ptr, v.length * ELEMENT_SIZE);
-            if (v.length < cols) native().call('gs_upload', this.ctx, m.ptr + BigInt((r * cols + v.length) * ELEMENT_SIZE), Buffer.alloc((cols - v.length) * ELEMENT_SIZE), (cols - v.length) * ELEMENT_SIZE);
+            this.lib.call('gs_copy', this.ctx, m.ptr + BigInt(r * cols * this.elementSize), v.ptr, v.length * this.elementSize);
+            if (v.length < cols) this.lib.call('gs_upload', this.ctx, m.ptr + BigInt((r * cols + v.length) * this.elementSize), Buffer.alloc((cols - v.length) * this.elementSize), (cols - v.length) * this.elementSize);
         });
         return m;
     }
-    matrixRowsToVectors(m) { const out = []; for (let r = 0; r < m.rowCount; r++) out.push(m.row(r)); return out; }
+    matrixRowsToVectors(m) { this._own(m); const out = []; for (let r = 0; r < m.rowCount; r++) out.push(m.row(r)); return out; }
     // ---- vector ops
     _binary(fnVec, fnScalar, a, b) {
+        this._own(a, b);
         const out = new Vector(this, a.length);
-        if (typeof b === 'bigint') native().call(fnScalar, this.ctx, a.ptr, le(this.mod(b)), a.length, out.ptr);
+        if (typeof b === 'bigint') this.lib.call(fnScalar, this.ctx, a.ptr, this.le(this.mod(b)), a.length, out.ptr);
         else {
             if (a.length !== b.length) throw new Error('Cannot combine vector elements: vectors have different lengths');
-            native().call(fnVec, this.ctx, a.ptr, b.ptr, a.length, out.ptr);
+            this.lib.call(fnVec, this.ctx, a.ptr, b.ptr, a.length, out.ptr);
         }
         return out;
     }
@@ -238,71 +319,81 @@ class PrimeField {
     subVectorElements(a, b) { return this._binary('gs_vec_sub', 'gs_vec_sub_scalar', a, b); }
     mulVectorElements(a, b) { return this._binary('gs_vec_mul', 'gs_vec_mul_scalar', a, b); }
     divVectorElements(a, b) {
+        this._own(a, b);
         if (typeof b === 'bigint') return this.mulVectorElements(a, this.inv(b));
         const out = new Vector(this, a.length);
-        native().call('gs_vec_div', this.ctx, a.ptr, b.ptr, a.length, out.ptr);
+        this.lib.call('gs_vec_div', this.ctx, a.ptr, b.ptr, a.length, out.ptr);
         return out;
     }
-    invVectorElements(a) { const out = new Vector(this, a.length); native().call('gs_vec_inv', this.ctx, a.ptr, a.length, out.ptr); return out; }
+    invVectorElements(a) { this._own(a); const out = new Vector(this, a.length); this.lib.call('gs_vec_inv', this.ctx, a.ptr, a.length, out.ptr); return out; }
     expVectorElements(a, e) {
+        this._own(a);
         if (e < 0n) { a = this.invVectorElements(a); e = -e; }
-        const out = new Vector(this, a.length); native().call('gs_vec_exp', this.ctx, a.ptr, le(e), a.length, out.ptr); return out;
+        const out = new Vector(this, a.length); this.lib.call('gs_vec_exp', this.ctx, a.ptr, this.le(e), a.length, out.ptr); return out;
     }
-    combineVectors(a, b) { const out = Buffer.alloc(ELEMENT_SIZE); native().call('gs_combine', this.ctx, a.ptr, b.ptr, a.length, out); return fromLe(out); }
-    mulMatrixByVector(m, v) {   // examples/poseidon/utils.ts:45
+    combineVectors(a, b) { this._own(a, b); const out = Buffer.alloc(this.elementSize); this.lib.call('gs_combine', this.ctx, a.ptr, b.ptr, a.length, out); return this.fromLe(out); }
+    mulMatrixByVector(m, v) { // examples/poseidon/utils.ts:45
+        this._own(m, v);
         const out = [];
-        for (let r = 0; r < m.rowCount; r++) out.push(this.combineVectors(new Vector(this, m.colCount, m.owner, m.offset + BigInt(r * m.colCount * ELEMENT_SIZE)), v));
+        for (let r = 0; r < m.rowCount; r++) out.push(this.combineVectors(new Vector(this, m.colCount, m.owner, m.offset + BigInt(r * m.colCount * this.elementSize)), v));
         return this.newVectorFrom(out);
     }
     combineManyVectors(vectors, coefficients) {
+        this._own(...vectors, coefficients);
         const ks = Array.isArray(coefficients) ? coefficients : coefficients.toValues();
         const out = new Vector(this, vectors[0].length);
-        native().call('gs_combine_many', this.ctx, vectors.map(v => v.ptr), packLe(ks), vectors.length, vectors[0].length, out.ptr);
+        this.lib.call('gs_combine_many', this.ctx, vectors.map(v => v.ptr), this.packLe(ks), vectors.length, vectors[0].length, out.ptr);
         return out;
     }
     getPowerSeries(base, length) {
         const out = new Vector(this, length);
-        native().call('gs_power_series', this.ctx, le(this.mod(base)), length, out.ptr);
+        this.lib.call('gs_power_series', this.ctx, this.le(this.mod(base)), length, out.ptr);
         out.seriesBase = this.mod(base);
         return out;
     }
-    pluckVector(v, skip, times) { const out = new Vector(this, times); native().call('gs_pluck', this.ctx, v.ptr, v.length, skip, times, out.ptr); return out; }
+    pluckVector(v, skip, times) { this._own(v); const out = new Vector(this, times); this.lib.call('gs_pluck', this.ctx, v.ptr, v.length, skip, times, out.ptr); return out; }
     transposeVector(v, columns, step = 1) {
+        this._own(v);
         const rows = v.length / (columns * step);
         const m = new Matrix(this, rows, columns);
-        native().call('gs_transpose_vector', this.ctx, v.ptr, v.length, columns, step, m.ptr);
+        this.lib.call('gs_transpose_vector', this.ctx, v.ptr, v.length, columns, step, m.ptr);
         if (columns === 4 && v.seriesBase !== undefined) m.quarticDomain = { omega: v.seriesBase, n: v.length, step };
         return m;
     }
     // ---- matrix ops
-    transposeMatrix(m) { const out = new Matrix(this, m.colCount, m.rowCount); native().call('gs_transpose_matrix', this.ctx, m.ptr, m.rowCount, m.colCount, out.ptr); return out; }
-    joinMatrixRows(m) { return new Vector(this, m.rowCount * m.colCount, m.owner, m.offset); }
+    transposeMatrix(m) { this._own(m); const out = new Matrix(this, m.colCount, m.rowCount); this.lib.call('gs_transpose_matrix', this.ctx, m.ptr, m.rowCount, m.colCount, out.ptr); return out; }
+    joinMatrixRows(m) { this._own(m); return new Vector(this, m.rowCount * m.colCount, m.owner, m.offset); }
     subMatrixElementsFromVectors(vectors, m) {
+        this._own(...vectors, m);
         const out = new Matrix(this, m.rowCount, m.colCount);
-        native().call('gs_sub_matrix_from_vectors', this.ctx, vectors.map(v => v.ptr), m.ptr, m.rowCount, m.colCount, out.ptr);
+        this.lib.call('gs_sub_matrix_from_vectors', this.ctx, vectors.map(v => v.ptr), m.ptr, m.rowCount, m.colCount, out.ptr);
         return out;
     }
-    divMatrixElements(a, b) { const out = new Matrix(this, a.rowCount, a.colCount); native().call('gs_vec_div', this.ctx, a.ptr, b.ptr, a.rowCount * a.colCount, out.ptr); return out; }
+    divMatrixElements(a, b) { this._own(a, b); const out = new Matrix(this, a.rowCount, a.colCount); this.lib.call('gs_vec_div', this.ctx, a.ptr, b.ptr, a.rowCount * a.colCount, out.ptr); return out; }
     // ---- polynomials
     _omegaOf(roots) { return roots.seriesBase !== undefined ? roots.seriesBase : (roots.length > 1 ? roots.getValue(1) : 1n); }
     evalPolyAtRoots(poly, roots) {
+        this._own(poly, roots);
         const out = new Vector(this, roots.length);
-        native().call('gs_eval_polys_at_roots', this.ctx, poly.ptr, 1, poly.length, le(this._omegaOf(roots)), roots.length, out.ptr);
+        this.lib.call('gs_eval_polys_at_roots', this.ctx, poly.ptr, 1, poly.length, this.le(this._omegaOf(roots)), roots.length, out.ptr);
         return out;
     }
     evalPolysAtRoots(polys, roots) {
+        this._own(polys, roots);
         const out = new Matrix(this, polys.rowCount, roots.length);
-        native().call('gs_eval_polys_at_roots', this.ctx, polys.ptr, polys.rowCount, polys.colCount, le(this._omegaOf(roots)), roots.length, out.ptr);
+        this.lib.call('gs_eval_polys_at_roots', this.ctx, polys.ptr, polys.rowCount, polys.colCount, this.le(this._omegaOf(roots)), roots.length, out.ptr);
         return out;
     }
     interpolateRoots(roots, ys) {
+        this._own(roots, ys);
         const n = roots.length, isM = ys instanceof Matrix;
         const out = isM ? new Matrix(this, ys.rowCount, n) : new Vector(this, n);
-        native().call('gs_interpolate_roots', this.ctx, ys.ptr, isM ? ys.rowCount : 1, le(this._omegaOf(roots)), n, out.ptr);
+        this.lib.call('gs_interpolate_roots', this.ctx, ys.ptr, isM ? ys.rowCount : 1, this.le(this._omegaOf(roots)), n, out.ptr);
         return out;
     }
-    evalPolyAt(poly, x) { const out = Buffer.alloc(ELEMENT_SIZE); native().call('gs_eval_poly_at', this.ctx, poly.ptr, poly.length, le(this.mod(x)), out); return fromLe(out); }
+    evalPolyAt(poly, x) { this._own(poly); const out = Buffer.alloc(this.elementSize); this.lib.call('gs_eval_poly_at', this.ctx, poly.ptr, poly.length, this.le(this.mod(x)), out); return this.fromLe(out); }
     mulPolys(a, b) {
+        this._own(a, b);
         // tiny operands (BoundaryConstraints.ts:30) on the host; larger ones through the device NTT
         const la = a.length, lb = b.length;
         if (la * lb <= 4096) {
@@ -316,30 +407,33 @@ class PrimeField {
         return new Vector(this, la + lb - 1, full.owner, full.offset);
     }
     padPoly(v, length) {
+        this._own(v);
         if (v.length === length) return v;
         const out = new Vector(this, length);
-        native().call('gs_copy', this.ctx, out.ptr, v.ptr, v.length * ELEMENT_SIZE);
-        const zeros = Buffer.alloc((length - v.length) * ELEMENT_SIZE);
-        native().call('gs_upload', this.ctx, out.ptr + BigInt(v.length * ELEMENT_SIZE), zeros, zeros.length);
+        this.lib.call('gs_copy', this.ctx, out.ptr, v.ptr, v.length * this.elementSize);
+        const zeros = Buffer.alloc((length - v.length) * this.elementSize);
+        this.lib.call('gs_upload', this.ctx, out.ptr + BigInt(v.length * this.elementSize), zeros, zeros.length);
         return out;
     }
     addPolys(a, b) { const n = Math.max(a.length, b.length); return this.addVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     subPolys(a, b) { const n = Math.max(a.length, b.length); return this.subVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     mulPolyByConstant(a, c) { return this.mulVectorElements(a, this.mod(c)); }
     interpolate(xs, ys) {
-        const n = xs.length, out = Buffer.alloc(ELEMENT_SIZE * n);
-        native().call('gs_small_interpolate', xs.toBuffer(), ys.toBuffer(), n, out);
-        const v = new Vector(this, n); native().call('gs_upload', this.ctx, v.ptr, out, out.length); return v;
+        this._own(xs, ys);
+        const n = xs.length, out = Buffer.alloc(this.elementSize * n);
+        this.lib.call('gs_small_interpolate', xs.toBuffer(), ys.toBuffer(), n, out);
+        const v = new Vector(this, n); this.lib.call('gs_upload', this.ctx, v.ptr, out, out.length); return v;
     }
     interpolateQuarticBatch(xs, ys) {
+        this._own(xs, ys);
         const out = new Matrix(this, ys.rowCount, 4);
-        if (xs.quarticDomain) native().call('gs_interpolate_quartic_domain', this.ctx, le(xs.quarticDomain.omega), xs.quarticDomain.n, xs.quarticDomain.step, ys.ptr, ys.rowCount, out.ptr);
-        else native().call('gs_interpolate_quartic_batch', this.ctx, xs.ptr, ys.ptr, ys.rowCount, out.ptr);
+        if (xs.quarticDomain) this.lib.call('gs_interpolate_quartic_domain', this.ctx, this.le(xs.quarticDomain.omega), xs.quarticDomain.n, xs.quarticDomain.step, ys.ptr, ys.rowCount, out.ptr);
+        else this.lib.call('gs_interpolate_quartic_batch', this.ctx, xs.ptr, ys.ptr, ys.rowCount, out.ptr);
         return out;
     }
-    evalQuarticBatch(polys, x) { const out = new Vector(this, polys.rowCount); native().call('gs_eval_quartic_batch', this.ctx, polys.ptr, polys.rowCount, le(this.mod(x)), out.ptr); return out; }
+    evalQuarticBatch(polys, x) { this._own(polys); const out = new Vector(this, polys.rowCount); this.lib.call('gs_eval_quartic_batch', this.ctx, polys.ptr, polys.rowCount, this.le(this.mod(x)), out.ptr); return out; }
 }
 
 function createPrimeField(modulus, options) { return new PrimeField(modulus, options); }
 
-module.exports = { createPrimeField, PrimeField, Vector, Matrix, MODULUS, LIBRARIES, native, le, packLe, unpackLe, fromLe, sha256 };
+module.exports = { createPrimeField, PrimeField, Vector, Matrix, MODULUS, LIBRARIES, native, le, packLe, unpackLe, fromLe, sha256, isProbablePrime };

@@ -1,9 +1,9 @@
 'use strict';
 // js/prover.js — ONE native call for a whole proof: Stark.prove() + Serializer.serializeProof() through the
 // native driver (include/gstark_prover.h, genstark_amd/csrc/prover.cc), reached through the same N-API addon that carries the
-// member-by-member galois / merkle surface.  The returned Buffer is what lib/Serializer.ts:83-144 (`stark.parse`) reads.
+// member-by-member galois / merkle surface: through the library object of the AIR's field (air.field.lib), so proofs in several fields
+// can alternate in one process.  The returned Buffer is what lib/Serializer.ts:83-144 (`stark.parse`) reads.
 const path = require('path');
-const { native, le, packLe } = require('./galois');
 
 const HASH_ALG = { sha256: 0, blake2s256: 1 };
 // one build of the driver per field flavour, like the ABI library (genstark_amd/csrc/build.sh)
@@ -24,11 +24,11 @@ function proveMimcSerialized(air, options, assertions, seed) {
     const f = air.field;
     const job = {
         steps: air.steps, extensionFactor: air.extensionFactor, exeQueryCount: options.exeQueryCount, friQueryCount: options.friQueryCount,
-        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: le(context.rootOfUnity), seed: le(f.mod(seed)),
-        roundConstants: air._rcPacked || (air._rcPacked = packLe(air.roundConstants)), kTable: context.kTable.ptr, kLen: context.kTable.length,
-        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: le(f.mod(a.value)) })),
+        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: f.le(context.rootOfUnity), seed: f.le(f.mod(seed)),
+        roundConstants: air._rcPacked || (air._rcPacked = f.packLe(air.roundConstants)), kTable: context.kTable.ptr, kLen: context.kTable.length,
+        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: f.le(f.mod(a.value)) })),
     };
-    return native().proveMimcSerialized(f.ctx, driverPath(f), job);
+    return f.lib.proveMimcSerialized(f.ctx, driverPath(f), job);
 }
 
 // ... and for an AIR given as register-machine programs (js/air_generic.js: the reference's Rescue / Poseidon examples): kind 1 of
@@ -47,18 +47,18 @@ function genericJob(air, context, options, assertions) {
             else if (code[i] === 8) code[i + 3] += base;       // POWC: exponent index
         }
         const all = t.consts.concat(e.consts);
-        air._jobPrograms = { eCode: code, consts: all.length ? packLe(all) : Buffer.alloc(0) };
+        air._jobPrograms = { eCode: code, consts: all.length ? f.packLe(all) : Buffer.alloc(0) };
     }
     const eCode = air._jobPrograms.eCode;
     const job = {
         steps: air.steps, extensionFactor: air.extensionFactor, exeQueryCount: options.exeQueryCount, friQueryCount: options.friQueryCount,
-        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: le(air.rootOfUnity),
-        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: le(f.mod(a.value)) })),
+        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: f.le(air.rootOfUnity),
+        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: f.le(f.mod(a.value)) })),
         registers: air.traceRegisterCount, degrees: air.constraintDegrees, tCode: t.code, iCode: init ? init.code : [], eCode,
         consts: air._jobPrograms.consts, vmRegs: Math.max(t.nregs, e.nregs, init ? init.nregs : 0),
         // static registers: the public ones, then this proof's secret columns (struct gs_prover_air: static_values / static_tables hold both)
         staticValues: context.staticValuesPacked(), staticPeriods: context.allStaticColumns().map(v => v.length), staticTables: context.staticTables.ptr,
-        staticLens: context.staticLens, firstRows: context.firstRows.packedFirstRows || packLe(flatRows(context.firstRows)),
+        staticLens: context.staticLens, firstRows: context.firstRows.packedFirstRows || f.packLe(flatRows(context.firstRows)),
         segments: air.segmentLength === null ? 0 : (context.firstRows.packedFirstRows ? context.firstRows.rows : context.firstRows.length),
         segmentLen: air.segmentLength === null ? 0 : air.segmentLength,
     };
@@ -67,7 +67,7 @@ function genericJob(air, context, options, assertions) {
 }
 function proveGenericSerialized(air, options, assertions, seed) {
     const context = air.jobContext ? air.jobContext(seed) : air.initProvingContext([], seed);
-    return native().proveGenericSerialized(air.field.ctx, driverPath(air.field), genericJob(air, context, options, assertions));
+    return air.field.lib.proveGenericSerialized(air.field.ctx, driverPath(air.field), genericJob(air, context, options, assertions));
 }
 
 // ... and for an air-assembly component WITH input registers (js/air_assembly.js: AssemblyAir): the loader lays the inputs out (the inner
@@ -80,7 +80,7 @@ function proveAssemblySerialized(assemblyAir, options, assertions, inputs, seed)
     const job = genericJob(context.air, context, options, assertions);
     job.inputRegisters = [].concat(...assemblyAir.info.inputDeclarations.map(declWords));
     job.inputShapes = [].concat(...context.inputShapes.map(sh => [sh.length].concat(sh)));
-    return native().proveGenericSerialized(context.air.field.ctx, driverPath(context.air.field), job);
+    return context.air.field.lib.proveGenericSerialized(context.air.field.ctx, driverPath(context.air.field), job);
 }
 function verifyAssemblySerialized(assemblyAir, options, assertions, proof, publicInputs) {
     if (!(options.hashAlgorithm in HASH_ALG)) throw new TypeError(`Hash algorithm ${options.hashAlgorithm} is not supported`);
@@ -95,17 +95,17 @@ function verifyAssemblySerialized(assemblyAir, options, assertions, proof, publi
     const cycles = info.cycles.map(c => c.map(BigInt));
     const job = {
         steps: 0, extensionFactor: assemblyAir.extensionFactor, exeQueryCount: options.exeQueryCount, friQueryCount: options.friQueryCount,
-        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: le(f.getRootOfUnity(2 ** log2)), rootOfUnityLog2: log2,
-        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: le(f.mod(a.value)) })),
+        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: f.le(f.getRootOfUnity(2 ** log2)), rootOfUnityLog2: log2,
+        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: f.le(f.mod(a.value)) })),
         registers: assemblyAir.traceRegisterCount, degrees: assemblyAir.constraintDegrees, tCode: [], iCode: [], eCode: e.code,
-        consts: e.consts.length ? Buffer.concat(e.consts.map(v => le(BigInt(v)))) : Buffer.alloc(0), vmRegs: e.nregs,
-        staticValues: cycles.length ? Buffer.concat([].concat(...cycles).map(v => le(f.mod(v)))) : le(0n), staticPeriods: cycles.map(c => c.length),
+        consts: e.consts.length ? Buffer.concat(e.consts.map(v => f.le(BigInt(v)))) : Buffer.alloc(0), vmRegs: e.nregs,
+        staticValues: cycles.length ? Buffer.concat([].concat(...cycles).map(v => f.le(f.mod(v)))) : f.le(0n), staticPeriods: cycles.map(c => c.length),
         staticTables: 0n, staticLens: cycles.map(() => 0), firstRows: Buffer.alloc(assemblyAir.traceRegisterCount * f.elementSize), segments: 0, segmentLen: 0,
         nsecret: assemblyAir.secretInputCount, inputRegisters: [].concat(...info.inputDeclarations.map(declWords)),
-        staticSources: [].concat(...info.staticSources), publicInputs: lists.length ? Buffer.concat(lists.map(l => packLe(l, v => f.mod(v)))) : Buffer.alloc(0),
+        staticSources: [].concat(...info.staticSources), publicInputs: lists.length ? Buffer.concat(lists.map(l => f.packLe(l, v => f.mod(v)))) : Buffer.alloc(0),
         publicInputCounts: lists.map(l => l.length),
     };
-    return native().proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
+    return f.lib.proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
 }
 
 // Stark.verify() of serialized proof bytes by the NATIVE verifier (genstark_amd/csrc/verifier.h; CPU only, no device work): true, or throws
@@ -114,26 +114,26 @@ function verifyMimcSerialized(air, options, assertions, proof) {
     const f = air.field, root = air._root !== undefined ? air._root : f.getRootOfUnity(air.steps * air.extensionFactor);
     const job = {
         steps: air.steps, extensionFactor: air.extensionFactor, exeQueryCount: options.exeQueryCount, friQueryCount: options.friQueryCount,
-        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: le(root), seed: le(0n),
-        roundConstants: Buffer.concat(air.roundConstants.map(le)), kTable: 0n, kLen: 0,
-        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: le(f.mod(a.value)) })),
+        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: f.le(root), seed: f.le(0n),
+        roundConstants: Buffer.concat(air.roundConstants.map(v => f.le(v))), kTable: 0n, kLen: 0,
+        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: f.le(f.mod(a.value)) })),
     };
-    return native().proveMimcSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
+    return f.lib.proveMimcSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
 }
 function verifyGenericSerialized(air, options, assertions, proof) {
     const f = air.field, e = air.evaluationProgram;
     const statics = [].concat(...air.staticRegisters);
     const job = {
         steps: air.steps, extensionFactor: air.extensionFactor, exeQueryCount: options.exeQueryCount, friQueryCount: options.friQueryCount,
-        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: le(air.rootOfUnity),
-        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: le(f.mod(a.value)) })),
+        hashAlg: HASH_ALG[options.hashAlgorithm], rootOfUnity: f.le(air.rootOfUnity),
+        assertions: assertions.map(a => ({ step: a.step, register: a.register, value: f.le(f.mod(a.value)) })),
         registers: air.traceRegisterCount, degrees: air.constraintDegrees, tCode: [], iCode: [], eCode: e.code,
-        consts: e.consts.length ? Buffer.concat(e.consts.map(le)) : Buffer.alloc(0), vmRegs: e.nregs,
-        staticValues: statics.length ? packLe(statics, v => f.mod(v)) : le(0n), staticPeriods: air.staticRegisters.map(v => v.length),
+        consts: e.consts.length ? Buffer.concat(e.consts.map(v => f.le(v))) : Buffer.alloc(0), vmRegs: e.nregs,
+        staticValues: statics.length ? f.packLe(statics, v => f.mod(v)) : f.le(0n), staticPeriods: air.staticRegisters.map(v => v.length),
         staticTables: 0n, staticLens: air.staticRegisters.map(() => 0), firstRows: Buffer.alloc(air.traceRegisterCount * f.elementSize),
         segments: 0, segmentLen: 0,
     };
-    return native().proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
+    return f.lib.proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
 }
 
 /** seed (as proveGenericSerialized takes it) -> the first rows packed once, for many proofs: what a caller whose inputs already are bytes

@@ -1,7 +1,9 @@
 // napi/gstark_napi.cc — thin N-API shim over the C ABI of include/gstark.h.
 //
 // This is the binding a genSTARK maintainer adds in place of the wasm loaders of @guildofweavers/galois and
-// @guildofweavers/merkle: it dlopen()s libgstark_hip.so and forwards calls 1:1.  No arithmetic happens here.
+// @guildofweavers/merkle: it dlopen()s libgstark_hip.so and forwards calls 1:1.  No arithmetic happens here.  open(path) returns one
+// object per loaded library (field flavour), so one process can work in several fields; the module-level members act on the library
+// of the last load().
 // JS-side conventions (used by js/galois.js and js/merkle.js, which rebuild the FiniteField / Hash / MerkleTree
 // objects lib/Stark.ts consumes):
 //   * a context is an External; a device pointer is a BigInt; sizes/counts are Numbers (or BigInts);
@@ -16,8 +18,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <map>
 #include <numeric>
 #include <string>
+#include <unordered_set>
 #include <vector>
 
 #include "../include/gstark.h"
@@ -25,7 +29,23 @@
 
 namespace {
 
-void *g_lib = nullptr;
+// One loaded implementation of include/gstark.h (a field flavour): its dl handle, the contexts it created, and its bindings of the
+// native driver (gs_prover_open against THIS handle, keyed by the driver's path).  open(path) returns it as an object whose members are
+// the module's; the module-level members act on the library of the last load().  Libraries and bindings live as long as the process:
+// proofs that alternate between fields never close or reopen anything.
+struct Driver {
+    void *dl = nullptr;
+    gs_prover_binding *binding = nullptr;
+};
+struct Lib {
+    void *dl = nullptr;
+    size_t es = 0;
+    std::string backend;
+    std::map<std::string, Driver> drivers;
+    std::unordered_set<void *> ctxs;       // gs_ctx layouts differ between flavours: a context is only ever handed to the library that made it
+};
+std::vector<Lib *> g_libs;
+Lib *g_cur = nullptr;                      // the module-level surface: the last load()
 
 #define NAPI_OK(env, call)                                                \
     do {                                                                  \
@@ -121,6 +141,25 @@ bool get_u64(napi_env env, napi_value v, uint64_t *out) {
     return false;
 }
 
+// the library a member acts on: a library object's (the function's data), else the module-level one; throws when there is none
+Lib *lib_of(napi_env env, void *data) {
+    Lib *L = data ? (Lib *)data : g_cur;
+    if (!L) napi_throw_error(env, nullptr, "call load(path) first");
+    return L;
+}
+// a context argument: an External this library created (never one of another library's, nor one it destroyed)
+enum CtxArg { CTX_OK, CTX_NOT_EXTERNAL, CTX_FOREIGN };
+CtxArg get_ctx(napi_env env, const Lib *L, napi_value v, void **out) {
+    void *p = nullptr;
+    if (napi_get_value_external(env, v, &p) != napi_ok || !p) return CTX_NOT_EXTERNAL;
+    if (!L->ctxs.count(p)) return CTX_FOREIGN;
+    *out = p;
+    return CTX_OK;
+}
+void throw_foreign(napi_env env, const char *what) {
+    napi_throw_type_error(env, nullptr, (std::string(what) + ": the context was not created by this library (a context belongs to one field's library)").c_str());
+}
+
 typedef int (*fn16)(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
 
@@ -129,9 +168,11 @@ typedef int (*fn16)(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintp
 napi_value Call(napi_env env, napi_callback_info info) {
     size_t argc = 20;
     napi_value argv[20];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    void *data;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, &data));
     if (argc < 1) { napi_throw_type_error(env, nullptr, "call(name, ...args)"); return nullptr; }
-    if (!g_lib) { napi_throw_error(env, nullptr, "call load(path) first"); return nullptr; }
+    Lib *L = lib_of(env, data);
+    if (!L) return nullptr;
     char name[64];
     size_t len;
     if (napi_get_value_string_utf8(env, argv[0], name, sizeof name, &len) != napi_ok) { napi_throw_type_error(env, nullptr, "call(name, ...args): the name is a string"); return nullptr; }
@@ -141,7 +182,7 @@ napi_value Call(napi_env env, napi_callback_info info) {
     if (!d) { napi_throw_error(env, nullptr, (std::string("unknown gstark function ") + name).c_str()); return nullptr; }
     const size_t n = strlen(d->sig);
     if (argc - 1 != n) { napi_throw_type_error(env, nullptr, (std::string(name) + ": wrong number of arguments").c_str()); return nullptr; }
-    void *sym = dlsym(g_lib, name);
+    void *sym = dlsym(L->dl, name);
     if (!sym) { napi_throw_error(env, nullptr, (std::string("symbol not found: ") + name).c_str()); return nullptr; }
     uintptr_t a[16] = {0};
     std::vector<std::vector<uint64_t>> arrays;
@@ -153,8 +194,10 @@ napi_value Call(napi_env env, napi_callback_info info) {
         napi_value v = argv[i + 1];
         switch (d->sig[i]) {
             case 'c': {
-                void *p;
-                if (napi_get_value_external(env, v, &p) != napi_ok || !p) { napi_throw_type_error(env, nullptr, (std::string(name) + ": expected a context").c_str()); return nullptr; }
+                void *p = nullptr;
+                const CtxArg c = get_ctx(env, L, v, &p);
+                if (c == CTX_NOT_EXTERNAL) { napi_throw_type_error(env, nullptr, (std::string(name) + ": expected a context").c_str()); return nullptr; }
+                if (c == CTX_FOREIGN) { throw_foreign(env, name); return nullptr; }
                 ctx = (gs_ctx *)p;
                 a[i] = (uintptr_t)p;
                 break;
@@ -206,7 +249,7 @@ napi_value Call(napi_env env, napi_callback_info info) {
     int rc = ((fn16)sym)(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15]);
     if (rc != GS_OK) {
         typedef const char *(*errfn)(const gs_ctx *);
-        errfn le = (errfn)dlsym(g_lib, "gs_last_error");
+        errfn le = (errfn)dlsym(L->dl, "gs_last_error");
         std::string msg = std::string(name) + " failed (" + std::to_string(rc) + ")";
         if (ctx && le) msg += std::string(": ") + le(ctx);
         napi_throw_error(env, nullptr, msg.c_str());
@@ -217,34 +260,53 @@ napi_value Call(napi_env env, napi_callback_info info) {
     return undef;
 }
 
-// load(path): dlopen libgstark_hip.so; returns the backend name
+// dlopen(path) -> the library's record (one per dl handle: the same path opened twice is the same library); throws and returns null on failure
+Lib *open_lib(napi_env env, napi_value path_value, const char *usage) {
+    char path[1024];
+    size_t len;
+    if (napi_get_value_string_utf8(env, path_value, path, sizeof path, &len) != napi_ok) { napi_throw_type_error(env, nullptr, usage); return nullptr; }
+    void *lib = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!lib) { napi_throw_error(env, nullptr, (std::string("cannot load ") + path + ": " + dlerror() + " (there is no CPU fallback)").c_str()); return nullptr; }
+    typedef const char *(*namefn)(void);
+    typedef int (*sizefn)(void);
+    namefn nf = (namefn)dlsym(lib, "gs_backend_name");
+    sizefn sf = (sizefn)dlsym(lib, "gs_element_size");
+    if (!nf || !sf) { napi_throw_error(env, nullptr, "not a gstark library"); return nullptr; }
+    for (Lib *L : g_libs)
+        if (L->dl == lib) { dlclose(lib); return L; }       // (drops the reference this dlopen added)
+    Lib *L = new Lib;
+    L->dl = lib;
+    L->es = (size_t)sf();
+    L->backend = nf();
+    g_libs.push_back(L);
+    return L;
+}
+
+// load(path): dlopen libgstark_hip.so for the module-level members; returns the backend name
 napi_value Load(napi_env env, napi_callback_info info) {
     size_t argc = 1;
     napi_value argv[1];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    char path[1024];
-    size_t len;
-    if (argc < 1 || napi_get_value_string_utf8(env, argv[0], path, sizeof path, &len) != napi_ok) { napi_throw_type_error(env, nullptr, "load(path)"); return nullptr; }
-    void *lib = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!lib) { napi_throw_error(env, nullptr, (std::string("cannot load ") + path + ": " + dlerror() + " (there is no CPU fallback)").c_str()); return nullptr; }
-    typedef const char *(*namefn)(void);
-    namefn nf = (namefn)dlsym(lib, "gs_backend_name");
-    if (!nf) { napi_throw_error(env, nullptr, "not a gstark library"); return nullptr; }
-    g_lib = lib;
+    if (argc < 1) { napi_throw_type_error(env, nullptr, "load(path)"); return nullptr; }
+    Lib *L = open_lib(env, argv[0], "load(path)");
+    if (!L) return nullptr;
+    g_cur = L;
     napi_value out;
-    NAPI_OK(env, napi_create_string_utf8(env, nf(), NAPI_AUTO_LENGTH, &out));
+    NAPI_OK(env, napi_create_string_utf8(env, L->backend.c_str(), NAPI_AUTO_LENGTH, &out));
     return out;
 }
 
-// fieldInfo(): { elementSize, modulus: Buffer } of the loaded library (gs_element_size / gs_field_modulus)
+// fieldInfo(): { elementSize, modulus: Buffer } of the library (gs_element_size / gs_field_modulus; a runtime-modulus library's modulus
+// is the one gs_set_modulus gave it)
 napi_value FieldInfo(napi_env env, napi_callback_info info) {
-    if (!g_lib) { napi_throw_error(env, nullptr, "no library loaded"); return nullptr; }
-    typedef int (*sizefn)(void);
+    void *data;
+    NAPI_OK(env, napi_get_cb_info(env, info, nullptr, nullptr, nullptr, &data));
+    Lib *L = data ? (Lib *)data : g_cur;
+    if (!L) { napi_throw_error(env, nullptr, "no library loaded"); return nullptr; }
     typedef int (*modfn)(uint8_t *);
-    sizefn sf = (sizefn)dlsym(g_lib, "gs_element_size");
-    modfn mf = (modfn)dlsym(g_lib, "gs_field_modulus");
-    if (!sf || !mf) { napi_throw_error(env, nullptr, "not a gstark library"); return nullptr; }
-    const int es = sf();
+    modfn mf = (modfn)dlsym(L->dl, "gs_field_modulus");
+    if (!mf) { napi_throw_error(env, nullptr, "not a gstark library"); return nullptr; }
+    const int es = (int)L->es;
     uint8_t mod[64] = {0};
     if (es <= 0 || es > 64 || mf(mod) != GS_OK) { napi_throw_error(env, nullptr, "gs_field_modulus failed"); return nullptr; }
     napi_value out, v;
@@ -260,18 +322,21 @@ napi_value FieldInfo(napi_env env, napi_callback_info info) {
 napi_value CtxCreate(napi_env env, napi_callback_info info) {
     size_t argc = 1;
     napi_value argv[1];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    void *data;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, &data));
     int32_t device = 0;
     if (argc >= 1) napi_get_value_int32(env, argv[0], &device);
-    if (!g_lib) { napi_throw_error(env, nullptr, "call load(path) first"); return nullptr; }
+    Lib *L = lib_of(env, data);
+    if (!L) return nullptr;
     typedef int (*createfn)(int, void *, gs_ctx **);
-    createfn cf = (createfn)dlsym(g_lib, "gs_ctx_create");
+    createfn cf = (createfn)dlsym(L->dl, "gs_ctx_create");
     gs_ctx *ctx = nullptr;
     int rc = cf(device, nullptr, &ctx);
     if (rc != GS_OK || !ctx) {
         napi_throw_error(env, nullptr, ("gs_ctx_create failed (" + std::to_string(rc) + "): no gfx950 device; there is no CPU fallback").c_str());
         return nullptr;
     }
+    L->ctxs.insert(ctx);
     napi_value out;
     NAPI_OK(env, napi_create_external(env, ctx, nullptr, nullptr, &out));
     return out;
@@ -280,12 +345,17 @@ napi_value CtxCreate(napi_env env, napi_callback_info info) {
 napi_value CtxDestroy(napi_env env, napi_callback_info info) {
     size_t argc = 1;
     napi_value argv[1];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    void *p;
-    if (!g_lib) { napi_throw_error(env, nullptr, "call load(path) first"); return nullptr; }
-    if (argc < 1 || napi_get_value_external(env, argv[0], &p) != napi_ok || !p) { napi_throw_type_error(env, nullptr, "ctxDestroy(ctx)"); return nullptr; }
+    void *data;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, &data));
+    void *p = nullptr;
+    Lib *L = lib_of(env, data);
+    if (!L) return nullptr;
+    const CtxArg c = argc < 1 ? CTX_NOT_EXTERNAL : get_ctx(env, L, argv[0], &p);
+    if (c == CTX_NOT_EXTERNAL) { napi_throw_type_error(env, nullptr, "ctxDestroy(ctx)"); return nullptr; }
+    if (c == CTX_FOREIGN) { throw_foreign(env, "ctxDestroy"); return nullptr; }
     typedef void (*dfn)(gs_ctx *);
-    ((dfn)dlsym(g_lib, "gs_ctx_destroy"))((gs_ctx *)p);
+    ((dfn)dlsym(L->dl, "gs_ctx_destroy"))((gs_ctx *)p);
+    L->ctxs.erase(p);
     napi_value undef;
     napi_get_undefined(env, &undef);
     return undef;
@@ -295,14 +365,18 @@ napi_value CtxDestroy(napi_env env, napi_callback_info info) {
 napi_value Alloc(napi_env env, napi_callback_info info) {
     size_t argc = 2;
     napi_value argv[2];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    void *p;
-    if (!g_lib) { napi_throw_error(env, nullptr, "call load(path) first"); return nullptr; }
+    void *data;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, &data));
+    void *p = nullptr;
+    Lib *L = lib_of(env, data);
+    if (!L) return nullptr;
     uint64_t bytes;
-    if (argc < 2 || napi_get_value_external(env, argv[0], &p) != napi_ok || !p || !get_u64(env, argv[1], &bytes)) { napi_throw_type_error(env, nullptr, "alloc(ctx, bytes)"); return nullptr; }
+    const CtxArg c = argc < 2 ? CTX_NOT_EXTERNAL : get_ctx(env, L, argv[0], &p);
+    if (c == CTX_NOT_EXTERNAL || !get_u64(env, argv[1], &bytes)) { napi_throw_type_error(env, nullptr, "alloc(ctx, bytes)"); return nullptr; }
+    if (c == CTX_FOREIGN) { throw_foreign(env, "alloc"); return nullptr; }
     typedef int (*afn)(gs_ctx *, uint64_t, void **);
     void *d = nullptr;
-    int rc = ((afn)dlsym(g_lib, "gs_alloc"))((gs_ctx *)p, bytes, &d);
+    int rc = ((afn)dlsym(L->dl, "gs_alloc"))((gs_ctx *)p, bytes, &d);
     if (rc != GS_OK) { napi_throw_error(env, nullptr, "gs_alloc failed"); return nullptr; }
     napi_value out;
     NAPI_OK(env, napi_create_bigint_uint64(env, (uint64_t)(uintptr_t)d, &out));
@@ -313,12 +387,16 @@ napi_value Alloc(napi_env env, napi_callback_info info) {
 napi_value MerkleProveBatch(napi_env env, napi_callback_info info) {
     size_t argc = 5;
     napi_value argv[5];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    void *p;
-    if (!g_lib) { napi_throw_error(env, nullptr, "call load(path) first"); return nullptr; }
+    void *data;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, &data));
+    void *p = nullptr;
+    Lib *L = lib_of(env, data);
+    if (!L) return nullptr;
     uint64_t leaves, nodes, n;
-    if (argc < 5 || napi_get_value_external(env, argv[0], &p) != napi_ok || !p || !get_u64(env, argv[1], &leaves) || !get_u64(env, argv[2], &nodes) ||
+    const CtxArg c = argc < 5 ? CTX_NOT_EXTERNAL : get_ctx(env, L, argv[0], &p);
+    if (c == CTX_NOT_EXTERNAL || !get_u64(env, argv[1], &leaves) || !get_u64(env, argv[2], &nodes) ||
         !get_u64(env, argv[3], &n) || n < 2 || (n & (n - 1)) || n > (1ull << 40)) { napi_throw_type_error(env, nullptr, "merkleProveBatch: bad arguments"); return nullptr; }
+    if (c == CTX_FOREIGN) { throw_foreign(env, "merkleProveBatch"); return nullptr; }
     uint32_t count;
     if (napi_get_array_length(env, argv[4], &count) != napi_ok || count > (1u << 20)) { napi_throw_type_error(env, nullptr, "merkleProveBatch: bad index list"); return nullptr; }
     std::vector<uint64_t> idx(count);
@@ -334,11 +412,11 @@ napi_value MerkleProveBatch(napi_env env, napi_callback_info info) {
     std::vector<uint32_t> lens(count ? count : 1);
     uint32_t ncols = 0;
     typedef int (*pfn)(gs_ctx *, const void *, const void *, uint64_t, const uint64_t *, uint32_t, uint8_t *, uint32_t *, uint32_t *, uint8_t *, uint64_t);
-    int rc = ((pfn)dlsym(g_lib, "gs_merkle_prove_batch"))((gs_ctx *)p, (const void *)(uintptr_t)leaves, (const void *)(uintptr_t)nodes, n, idx.data(),
+    int rc = ((pfn)dlsym(L->dl, "gs_merkle_prove_batch"))((gs_ctx *)p, (const void *)(uintptr_t)leaves, (const void *)(uintptr_t)nodes, n, idx.data(),
                                                           count, values.data(), &ncols, lens.data(), nd.data(), cap);
     if (rc != GS_OK) {
         typedef const char *(*errfn)(const gs_ctx *);
-        napi_throw_error(env, nullptr, ((errfn)dlsym(g_lib, "gs_last_error"))((gs_ctx *)p));
+        napi_throw_error(env, nullptr, ((errfn)dlsym(L->dl, "gs_last_error"))((gs_ctx *)p));
         return nullptr;
     }
     uint64_t total = 0;
@@ -360,74 +438,70 @@ napi_value MerkleProveBatch(napi_env env, napi_callback_info info) {
 }
 
 // proveMimcSerialized(ctx, proverLibPath, job) -> Buffer: ONE call = Stark.prove() + Serializer.serializeProof() of the MiMC AIR through
-// the native driver (include/gstark_prover.h; the driver is bound to the ABI library load() opened).
+// the native driver (include/gstark_prover.h; the driver is bound to the ABI library the member belongs to: a library object's, or the
+// one load() opened).
 //   job = { steps, extensionFactor, exeQueryCount, friQueryCount, hashAlg, rootOfUnity: Buffer(es), seed: Buffer(es),
-//           roundConstants: Buffer(es*n), kTable: BigInt (device pointer), kLen, assertions: [{step, register, value: Buffer(es)}] }   (es = gs_element_size() of the loaded library)
-// The driver library is the build for the loaded ABI library's field (js/prover.js picks libgstark_prover*.so by modulus); the addon
-// holds ONE binding of it to that ABI library (gs_prover_open: nothing process-wide is written).  Scalars of a job are gs_element_size()
-// bytes each.
-void *g_prover = nullptr;
-gs_prover_binding *g_binding = nullptr;
-size_t g_es = 16;
+//           roundConstants: Buffer(es*n), kTable: BigInt (device pointer), kLen, assertions: [{step, register, value: Buffer(es)}] }   (es = gs_element_size() of that library)
+// The driver library is the build for that ABI library's field (js/prover.js picks libgstark_prover*.so by modulus); each ABI library
+// keeps its own binding of it (gs_prover_open: nothing process-wide is written), opened on first use and kept.  Scalars of a job are
+// gs_element_size() bytes each.
 typedef int (*prove_on_fn)(const gs_prover_binding *, gs_ctx *, const gs_prover_job *, uint8_t *, uint64_t, uint64_t *, char *, uint64_t);
-std::string g_prover_path;          // the driver build g_binding belongs to ...
-void *g_prover_for_lib = nullptr;   // ... and the ABI library it is bound to: load() may have replaced g_lib by another field's since
-bool open_driver(napi_env env, napi_value path_value) {
+const Driver *open_driver(napi_env env, Lib *L, napi_value path_value) {
     char path[1024];
     size_t len;
-    if (napi_get_value_string_utf8(env, path_value, path, sizeof path, &len) != napi_ok) { napi_throw_type_error(env, nullptr, "driver library path expected"); return false; }
-    if (g_prover && g_prover_for_lib == g_lib && g_prover_path == path) return true;
-    if (g_prover) {      // a binding of another driver flavour, or to a library that is no longer the loaded one: never reused
-        typedef void (*closefn)(gs_prover_binding *);
-        closefn cf = (closefn)dlsym(g_prover, "gs_prover_close");
-        if (cf && g_binding) cf(g_binding);
-        dlclose(g_prover);
-        g_prover = nullptr; g_binding = nullptr; g_prover_for_lib = nullptr; g_prover_path.clear();
-    }
+    if (napi_get_value_string_utf8(env, path_value, path, sizeof path, &len) != napi_ok) { napi_throw_type_error(env, nullptr, "driver library path expected"); return nullptr; }
+    auto hit = L->drivers.find(path);
+    if (hit != L->drivers.end()) return &hit->second;
     void *lib = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!lib) { napi_throw_error(env, nullptr, (std::string("cannot load ") + path + ": " + dlerror()).c_str()); return false; }
+    if (!lib) { napi_throw_error(env, nullptr, (std::string("cannot load ") + path + ": " + dlerror()).c_str()); return nullptr; }
     typedef int (*openfn)(void *, gs_prover_binding **);
-    typedef int (*sizefn)();
     openfn of = (openfn)dlsym(lib, "gs_prover_open");
-    sizefn sf = (sizefn)dlsym(g_lib, "gs_element_size");
-    if (!of || !sf || of(g_lib, &g_binding) != GS_OK) {
+    Driver d;
+    if (!of || of(L->dl, &d.binding) != GS_OK || !dlsym(lib, "gs_prover_prove_on") || !dlsym(lib, "gs_prover_verify_on")) {
         napi_throw_error(env, nullptr, "gs_prover_open failed: the driver library is not the build for the loaded library's field");
         dlclose(lib);
-        return false;
+        return nullptr;
     }
-    g_es = (size_t)sf();
-    g_prover = lib;
-    g_prover_path = path;
-    g_prover_for_lib = g_lib;
-    return true;
+    d.dl = lib;
+    return &(L->drivers[path] = d);
 }
 typedef int (*verify_on_fn)(const gs_prover_binding *, const gs_prover_job *, const uint8_t *, uint64_t, char *, uint64_t);
 // a 4th argument (a Buffer holding a serialized proof) turns either call below into Stark.verify() of that proof for the statement the job
 // describes (include/gstark_prover.h: gs_prover_verify_on — native, CPU only): returns true or throws the reference's message
-napi_value verify_instead(napi_env env, napi_value proof_value, const gs_prover_job &job) {
+napi_value verify_instead(napi_env env, const Driver *drv, napi_value proof_value, const gs_prover_job &job) {
     void *d;
     size_t len;
     if (!buffer_info(env, proof_value, &d, &len)) { napi_throw_type_error(env, nullptr, "the proof must be a Buffer"); return nullptr; }
     char err[512] = {0};
-    const int rc = ((verify_on_fn)dlsym(g_prover, "gs_prover_verify_on"))(g_binding, &job, (const uint8_t *)d, len, err, sizeof err);
+    const int rc = ((verify_on_fn)dlsym(drv->dl, "gs_prover_verify_on"))(drv->binding, &job, (const uint8_t *)d, len, err, sizeof err);
     if (rc != GS_OK) { napi_throw_error(env, nullptr, err[0] ? err : "verification failed"); return nullptr; }
     napi_value t;
     NAPI_OK(env, napi_get_boolean(env, true, &t));
     return t;
 }
-napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    void *ctx;
-    if (!g_lib) { napi_throw_error(env, nullptr, "call load(path) first"); return nullptr; }
+// the (ctx, proverLibPath, job[, proof]) head of both one-call entries: the library, its context, its binding of the driver
+const Driver *one_call_head(napi_env env, napi_callback_info info, size_t *argc, napi_value *argv, Lib **L, void **ctx) {
+    void *data;
+    if (napi_get_cb_info(env, info, argc, argv, nullptr, &data) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_cb_info"); return nullptr; }
+    *L = lib_of(env, data);
+    if (!*L) return nullptr;
     napi_valuetype job_type;
-    if (argc < 3 || napi_get_value_external(env, argv[0], &ctx) != napi_ok || !ctx || napi_typeof(env, argv[2], &job_type) != napi_ok || job_type != napi_object) {
+    const CtxArg c = *argc < 3 ? CTX_NOT_EXTERNAL : get_ctx(env, *L, argv[0], ctx);
+    if (c == CTX_NOT_EXTERNAL || napi_typeof(env, argv[2], &job_type) != napi_ok || job_type != napi_object) {
         napi_throw_type_error(env, nullptr, "(ctx, proverLibPath, job[, proof])");
         return nullptr;
     }
-    if (!open_driver(env, argv[1])) return nullptr;
-    const size_t es = g_es;
+    if (c == CTX_FOREIGN) { throw_foreign(env, "prove"); return nullptr; }
+    return open_driver(env, *L, argv[1]);
+}
+napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    void *ctx = nullptr;
+    Lib *L = nullptr;
+    const Driver *drv = one_call_head(env, info, &argc, argv, &L, &ctx);
+    if (!drv) return nullptr;
+    const size_t es = L->es;
     auto prop = [&](const char *name) { napi_value v; napi_get_named_property(env, argv[2], name, &v); return v; };
     auto u64 = [&](const char *name, uint64_t *out) { return get_u64(env, prop(name), out); };
     auto bytes = [&](napi_value v, const uint8_t **data, size_t *len) { void *d; bool ok = buffer_info(env, v, &d, len); *data = (const uint8_t *)d; return ok; };
@@ -468,12 +542,12 @@ napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
         as[i].step = step; as[i].reg = (uint32_t)reg; memcpy(as[i].value, val, es);
     }
     job.assertions = as.data(); job.nassertions = na;
-    if (argc >= 4) return verify_instead(env, argv[3], job);
+    if (argc >= 4) return verify_instead(env, drv, argv[3], job);
     static thread_local std::vector<uint8_t> out;      // (kept between calls: a fresh vector of this size is 4 MB of zeroing per proof)
     if (out.size() < (1u << 22)) out.resize(1u << 22);
     uint64_t n = 0;
     char err[512] = {0};
-    int rcode = ((prove_on_fn)dlsym(g_prover, "gs_prover_prove_on"))(g_binding, (gs_ctx *)ctx, &job, out.data(), out.size(), &n, err, sizeof err);
+    int rcode = ((prove_on_fn)dlsym(drv->dl, "gs_prover_prove_on"))(drv->binding, (gs_ctx *)ctx, &job, out.data(), out.size(), &n, err, sizeof err);
     if (rcode != GS_OK) { napi_throw_error(env, nullptr, (std::string("native prove() failed: ") + err).c_str()); return nullptr; }
     napi_value buf;
     NAPI_OK(env, napi_create_buffer_copy(env, (size_t)n, out.data(), nullptr, &buf));
@@ -488,16 +562,11 @@ napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
 napi_value ProveGenericSerialized(napi_env env, napi_callback_info info) {
     size_t argc = 4;
     napi_value argv[4];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    void *ctx;
-    if (!g_lib) { napi_throw_error(env, nullptr, "call load(path) first"); return nullptr; }
-    napi_valuetype job_type;
-    if (argc < 3 || napi_get_value_external(env, argv[0], &ctx) != napi_ok || !ctx || napi_typeof(env, argv[2], &job_type) != napi_ok || job_type != napi_object) {
-        napi_throw_type_error(env, nullptr, "(ctx, proverLibPath, job[, proof])");
-        return nullptr;
-    }
-    if (!open_driver(env, argv[1])) return nullptr;
-    const size_t es = g_es;
+    void *ctx = nullptr;
+    Lib *L = nullptr;
+    const Driver *drv = one_call_head(env, info, &argc, argv, &L, &ctx);
+    if (!drv) return nullptr;
+    const size_t es = L->es;
     auto prop = [&](const char *name) { napi_value v; napi_get_named_property(env, argv[2], name, &v); return v; };
     auto u64 = [&](const char *name, uint64_t *out) { return get_u64(env, prop(name), out); };
     auto bytes = [&](napi_value v, const uint8_t **data, size_t *len) { void *d; bool ok = buffer_info(env, v, &d, len); *data = (const uint8_t *)d; return ok; };
@@ -627,12 +696,12 @@ napi_value ProveGenericSerialized(napi_env env, napi_callback_info info) {
         as[i].step = step; as[i].reg = (uint32_t)reg; memcpy(as[i].value, val, es);
     }
     job.assertions = as.data(); job.nassertions = na;
-    if (argc >= 4) return verify_instead(env, argv[3], job);
+    if (argc >= 4) return verify_instead(env, drv, argv[3], job);
     static thread_local std::vector<uint8_t> out;      // (kept between calls: a fresh vector of this size is 4 MB of zeroing per proof)
     if (out.size() < (1u << 22)) out.resize(1u << 22);
     uint64_t n = 0;
     char err[512] = {0};
-    int rcode = ((prove_on_fn)dlsym(g_prover, "gs_prover_prove_on"))(g_binding, (gs_ctx *)ctx, &job, out.data(), out.size(), &n, err, sizeof err);
+    int rcode = ((prove_on_fn)dlsym(drv->dl, "gs_prover_prove_on"))(drv->binding, (gs_ctx *)ctx, &job, out.data(), out.size(), &n, err, sizeof err);
     if (rcode != GS_OK) { napi_throw_error(env, nullptr, (std::string("native prove() failed: ") + err).c_str()); return nullptr; }
     napi_value buf;
     NAPI_OK(env, napi_create_buffer_copy(env, (size_t)n, out.data(), nullptr, &buf));
@@ -706,9 +775,49 @@ napi_value UnpackElements(napi_env env, napi_callback_info info) {
     return arr;
 }
 
+// modulus getter of a library object: the library's modulus as little-endian bytes (a runtime-modulus library's after gs_set_modulus)
+napi_value LibModulus(napi_env env, napi_callback_info info) {
+    napi_value info_obj = FieldInfo(env, info), v;
+    if (!info_obj) return nullptr;
+    NAPI_OK(env, napi_get_named_property(env, info_obj, "modulus", &v));
+    return v;
+}
+
+// open(path) -> a library object: { backend, elementSize, modulus (getter: Buffer), fieldInfo(), ctxCreate(), ctxDestroy(), alloc(),
+// call(), merkleProveBatch(), proveMimcSerialized(), proveGenericSerialized() } — the module's members, on THIS library (a library
+// object's members refuse contexts another library created).  Several can be open at once: one per field flavour.
+napi_value Open(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 1) { napi_throw_type_error(env, nullptr, "open(path)"); return nullptr; }
+    Lib *L = open_lib(env, argv[0], "open(path)");
+    if (!L) return nullptr;
+    napi_value backend, es;
+    NAPI_OK(env, napi_create_string_utf8(env, L->backend.c_str(), NAPI_AUTO_LENGTH, &backend));
+    NAPI_OK(env, napi_create_uint32(env, (uint32_t)L->es, &es));
+    const napi_property_descriptor props[] = {
+        {"backend", nullptr, nullptr, nullptr, nullptr, backend, napi_enumerable, nullptr},
+        {"elementSize", nullptr, nullptr, nullptr, nullptr, es, napi_enumerable, nullptr},
+        {"modulus", nullptr, nullptr, LibModulus, nullptr, nullptr, napi_enumerable, L},
+        {"fieldInfo", nullptr, FieldInfo, nullptr, nullptr, nullptr, napi_default, L},
+        {"ctxCreate", nullptr, CtxCreate, nullptr, nullptr, nullptr, napi_default, L},
+        {"ctxDestroy", nullptr, CtxDestroy, nullptr, nullptr, nullptr, napi_default, L},
+        {"alloc", nullptr, Alloc, nullptr, nullptr, nullptr, napi_default, L},
+        {"call", nullptr, Call, nullptr, nullptr, nullptr, napi_default, L},
+        {"merkleProveBatch", nullptr, MerkleProveBatch, nullptr, nullptr, nullptr, napi_default, L},
+        {"proveMimcSerialized", nullptr, ProveMimcSerialized, nullptr, nullptr, nullptr, napi_default, L},
+        {"proveGenericSerialized", nullptr, ProveGenericSerialized, nullptr, nullptr, nullptr, napi_default, L},
+    };
+    napi_value out;
+    NAPI_OK(env, napi_create_object(env, &out));
+    NAPI_OK(env, napi_define_properties(env, out, sizeof props / sizeof props[0], props));
+    return out;
+}
+
 napi_value Init(napi_env env, napi_value exports) {
     const struct { const char *name; napi_callback cb; } fns[] = {
-        {"load", Load}, {"fieldInfo", FieldInfo}, {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"alloc", Alloc}, {"call", Call},
+        {"load", Load}, {"open", Open}, {"fieldInfo", FieldInfo}, {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"alloc", Alloc}, {"call", Call},
         {"merkleProveBatch", MerkleProveBatch}, {"proveMimcSerialized", ProveMimcSerialized}, {"proveGenericSerialized", ProveGenericSerialized},
         {"packElements", PackElements}, {"unpackElements", UnpackElements},
     };
