@@ -45,8 +45,7 @@ static const char *kFieldHeader =
 #include "jit_gf128.inc"
 #endif
     ;
-#if !defined(GS_SMALL_Q) && !defined(GS_WIDE_BITS)
-#define GS_JIT_LAZY 1          // the 128-bit field: long exponentiations run in the five-limb lazy form (gf128_lazy.h: lz_sqr, lz_mul_v)
+#ifdef GS_FIELD_128      // long exponentiations run in the five-limb lazy form (gf128_lazy.h: lz_sqr, lz_mul_v)
 static const char *kLazyHeader =
 #include "jit_gf128_lazy.inc"
     ;
@@ -97,7 +96,7 @@ static std::string jit_preamble() {
 #elif defined(GS_WIDE_BITS)
     s += "#define GS_WIDE_BITS " GS_STR(GS_WIDE_BITS) "\n";
 #endif
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
     s += "#include \"gf128_lazy.h\"\n";        // brings gf128.h with it
 #else
     s += "#include \"gs_field.h\"\n";
@@ -123,7 +122,7 @@ static std::string jit_preamble() {
          "    for (int i = 0; i < (int)(sizeof(fe) / 4); i++) pa[i] = c ? pa[i] : pb[i];\n"
          "    return a;\n"
          "}\n";
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
     // f * x for a selector f (a static register whose table is all 0 / 1 when the source is generated): a select; any other value of
     // f — the table is data, it may change without the program changing — takes the product, so the result never depends on the guess
     s += "__device__ __forceinline__ fe gs_blend(const fe f, const fe x) {\n"
@@ -132,7 +131,7 @@ static std::string jit_preamble() {
          "}\n";
 #endif
     // sum_k x_k * c_k on ONE lane (a fused row of a linear layer, ssa_fuse_dots)
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
     // 128-bit field: the constants in W-form (five pre-shifted copies: no high columns), every term 25 v_mad into five shared 64-bit
     // columns, ONE fold for up to six terms (columns stay below 2^57: 6 * 5 * 2^52).  The rows of a W-form built in registers are
     // laundered through an empty asm: with their value ranges visible hipcc (ROCm 7.2) miscompiles the products (ntt.hip has the same note)
@@ -225,7 +224,7 @@ struct JitGen {
     const uint64_t *soff = nullptr, *slen = nullptr;
     uint32_t nstatic = 0;
     bool static_is_binary(uint32_t reg) const {
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
         if (!statics || !soff || !slen || reg >= nstatic) return false;
         for (uint64_t i = 0; i < slen[reg]; i++) {
             const uint8_t *v = statics + (soff[reg] + i) * GS_ELT;
@@ -340,7 +339,7 @@ static void emit_pow(std::string &s, const char *x, const std::vector<uint32_t> 
         if (pl.cost < best.cost) best = pl;
     }
     if (best.steps.size() == 1 && best.steps[0].second == 1) return;     // x^1
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
     // A long chain (Rescue's inverse S-box: 127 squarings + 32 products) runs in the lazy five-limb form from end to end: one unpack,
     // lz_sqr (15 products + fold: ~53 instructions against the 84 of a canonical fe_mul) and lz_mul_v, one pack.  On a single wave per
     // SIMD a chain of dependent products costs its instruction count, so this is the length of the trace kernel's critical path.
@@ -510,9 +509,6 @@ static void ssa_recompute_depths(std::vector<SsaNode> &nodes) {
 // of a layer side by side on K lanes, one exchange for the whole layer.  Leaves that are not products by constants ride along with the
 // constant one.  Trees with fewer than two genuine products are left alone.
 static void ssa_fuse_dots(std::vector<SsaNode> &nodes) {
-#ifdef GS_NTT_EXPERIMENTS
-    if (const char *e = getenv("GSTARK_AIR_JIT_FUSE")) if (e[0] == '0') return;       // experiments build only: the unfused programs (A/B of the generator)
-#endif
     const int n = (int)nodes.size();
     std::vector<int> uses(n, 0), ops;
     for (const SsaNode &x : nodes) { ssa_operands(x, ops); for (int o : ops) uses[o]++; }
@@ -880,7 +876,7 @@ static void ssa_emit(std::string &s, std::string &hoisted, std::vector<bool> &co
 // hiprtc: source -> gfx950 code object (no device needed); false + log on failure
 static bool jit_compile(const std::string &source, const char *entry, std::vector<char> &code, std::string &log) {
     hiprtcProgram prog;
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
     const char *header_names[] = {"gf128.h", "gf128_lazy.h"};
     const char *headers[] = {kFieldHeader, kLazyHeader};
     const int nheaders = 2;
@@ -978,7 +974,7 @@ static int jit_compile_helper(const std::string &source, const char *entry, cons
     const int fd = sv[0];
     std::vector<std::pair<std::string, const char *>> items;
     items.push_back({entry, source.c_str()});
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
     items.push_back({"gf128.h", kFieldHeader});
     items.push_back({"gf128_lazy.h", kLazyHeader});
 #else
@@ -1044,7 +1040,7 @@ static std::string jit_cache_path(const std::string &source, const char *entry) 
     }
     // the key covers everything the code object depends on: the generated source AND the field headers it is compiled against
     std::string keyed = std::string(entry) + "|gfx950|v2|" + kFieldHeader;
-#ifdef GS_JIT_LAZY
+#ifdef GS_FIELD_128
     keyed += kLazyHeader;
 #endif
     keyed += "|" + source;

@@ -69,7 +69,7 @@ static hfe mimc_chunk_generic(hfe *t, hfe x, const hfe *rc, uint32_t nrc, uint32
     uint32_t ri = *ri_io;
     GS_MIMC_CHUNK_BODY(hf_mimc_step_weak)
 }
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__) && !defined(GS_SMALL_Q) && !defined(GS_WIDE_BITS)
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__) && defined(GS_FIELD_128)
 #define GS_MIMC_CHUNK_V3 1
 __attribute__((target("arch=x86-64-v3,tune=znver5"))) static hfe mimc_chunk_v3(hfe *t, hfe x, const hfe *rc, uint32_t nrc, uint32_t *ri_io, uint64_t base,
                                                                                uint64_t end) {

@@ -6,8 +6,7 @@
 // constant pool are wave-uniform (scalar loads), the scratch file lives in private memory.  Trace generation: steps are
 // sequentially dependent, one host core interprets the program on native 64-bit limbs.
 #include "common.h"
-#if !defined(GS_SMALL_Q) && !defined(GS_WIDE_BITS)
-#define GS_VM_LAZY 1       // long exponentiations of the interpreter in the lazy five-limb form (pow_group)
+#ifdef GS_FIELD_128      // long exponentiations of the interpreter in the lazy five-limb form (pow_group)
 #include "gf128_lazy.h"
 #endif
 #include "host_field.h"
@@ -68,7 +67,7 @@ __device__ __forceinline__ void pow_group(fe (&x)[4], const fe &e) {
     // (every S-box exponent and its inverse) start with r = x and keep the inner loop free of the "first product" test (wave-uniform).
     uint32_t bits = ev[0];
     const bool odd = bits & 1u;
-#ifdef GS_VM_LAZY
+#ifdef GS_FIELD_128
     // exponents longer than a word (Rescue's inverse S-box: 127 squarings + ~64 products): the whole chain in the lazy five-limb form
     // of gf128_lazy.h — lz_sqr is ~53 instructions against the 84 of a canonical product, and a chain of dependent products on one
     // wave per SIMD costs its instruction count (interpreted trace of 2 048 Rescue hashes: 3.6 -> 2.4 ms)

@@ -20,6 +20,7 @@
 #include "gf_wide.h"    // build flavour for the 256- / 224-bit primes (same names, 32-byte elements)
 #else
 #include "gf128.h"
+#define GS_FIELD_128 1  // the 128-bit field of the hot path, where units also compute in the lazy five-limb form (gf128_lazy.h)
 #endif
 
 #if defined(GF_RUNTIME_MODULUS)

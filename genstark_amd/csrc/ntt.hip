@@ -20,12 +20,9 @@
 //     into the first pass: out-of-range loads are predicated off, nothing is padded in memory.
 //   * The inverse transform is the same kernel on omega^-1 with the 1/n scale fused into the last
 //     pass's stores.
-#include <stdlib.h>
-
 #include "common.h"
 
-#if !defined(GS_SMALL_Q) && !defined(GS_WIDE_BITS)
-#define GS_NTT_LAZY 1      // the 128-bit field of the hot path: butterflies in five-limb lazy form (gf128_lazy.h)
+#ifdef GS_FIELD_128        // butterflies in five-limb lazy form (gf128_lazy.h)
 #include "gf128_lazy.h"
 struct alignas(32) lz8 { int32_t l[8]; };   // an NN element as a table entry: five limbs, 32-byte stride
 #endif
@@ -39,31 +36,19 @@ struct NttPlan {
     int npass = 0;
     int L[4] = {0, 0, 0, 0};
     fe *wR[4] = {nullptr, nullptr, nullptr, nullptr};  // (omega^(n/R))^i, i < R, per pass
+#ifndef GS_FIELD_128
     fe *twp[4] = {nullptr, nullptr, nullptr, nullptr}; // inter-pass twiddles omega_{Ns*R}^(jq*k) as a [k][jq] table (passes >= 1, when small)
+#endif
     fe w16[8];                                         // omega_16^i
     fe *inv_table = nullptr;                           // 1 / (omega^j - 1), j < n, [0] = 0 (built on first use: gs_plan_inverse_table)
     std::map<std::string, fe *> inv_table_shifted;     // 1 / (shift * omega^j - 1) per shift != 1 (gs_plan_inverse_table_shifted: a rank's coset)
-#ifdef GS_NTT_LAZY
+#ifdef GS_FIELD_128
     lzw *wtab = nullptr;                               // device: W-forms of omega_16^1..7 and of 1/n (read with scalar loads)
     lz8 *wRz[4] = {nullptr, nullptr, nullptr, nullptr};   // wR[i] * 2^130 as NN limbs (signed digits): the multipliers of lz_mul_vm
     fe *twpR[4] = {nullptr, nullptr, nullptr, nullptr};   // twp[i] * 2^130: per-lane twiddles go through the Montgomery product (gf128_lazy.h)
     fe *tw_loR = nullptr;                                 // tw_lo * 2^130 (start value of the running-product twiddles)
     lz8 *wRz_scaled = nullptr;                         // the last pass's table times 1/n (inverse transforms: the scale rides on the exchange twiddle)
-#ifdef GS_NTT_EXPERIMENTS
-    int4 *mf_tab = nullptr;                            // matrix-core passes (tools/ntt_mfma.h): the 4 KB operand table of omega_16
-    fe *mf_wR_scaled = nullptr;                        // omega_256^e / n
-    int mf_offs[16];
-    fe mf_bias0;
 #endif
-#endif
-};
-
-struct PassArgs {
-    uint64_t n, in_len, in_stride, out_stride;
-    int logn, logNs, logWj, log_lo, scale;
-    const fe *tw_lo, *tw_hi, *wR, *twp;
-    fe w16[8];
-    fe ninv;
 };
 
 int gs_power_series_dev(gs_ctx *c, const fe &base, uint64_t n, fe *out);  // pointwise.hip
@@ -81,33 +66,11 @@ __host__ __device__ constexpr int brev(int i, int bits) {
     return r;
 }
 
-// Fully unrolled decimation-in-frequency network on N = 2^LOGN registers.  w16[i] = omega_16^i.
-// Result is bit-reversed: X[q] = x[brev(q, LOGN)].
-template <int LOGN>
-__device__ __forceinline__ void ntt_dif_reg(fe (&x)[1 << LOGN], const fe (&w16)[8]) {
-    constexpr int N = 1 << LOGN;
-#pragma unroll
-    for (int s = N / 2; s >= 1; s >>= 1) {
-#pragma unroll
-        for (int b = 0; b < N; b += 2 * s) {
-#pragma unroll
-            for (int i = 0; i < s; i++) {
-                fe u = x[b + i], v = x[b + i + s];
-                x[b + i] = fe_add(u, v);
-                fe d = fe_sub(u, v);
-                const int tw = i * (N / 2 / s) * (16 / N);
-                x[b + i + s] = tw ? fe_mul(d, w16[tw]) : d;
-            }
-        }
-    }
-}
-
-
-#ifdef GS_NTT_LAZY
+#ifdef GS_FIELD_128
 // ======================================================================================================================
 // The pass kernel of the 128-bit field, butterflies in the lazy five-limb form of gf128_lazy.h.
 //
-// Same decomposition, indexing and LDS exchange as k_ntt_pass below (which stays for the other field flavours); what changes
+// Same decomposition, indexing and LDS exchange as k_ntt_pass, the pass kernel of the other field flavours (below); what changes
 // is the arithmetic and therefore the shape of a workgroup:
 //   * elements are unpacked to 5 x 26-bit limbs right after the 16-byte load and packed (canonical) right before the store;
 //     add/sub inside the networks are 5 plain 32-bit operations, no carries, no reduction;
@@ -407,18 +370,9 @@ __global__ __launch_bounds__(128, 2) void k_ntt_pass_lz(const fe *__restrict__ i
 // the dispatcher places on the same XCD one after the other, so the two halves of a 128-byte line meet in that XCD's L2.
 // The first pass writes its tile (contiguous in q for RB = 16) straight from registers; first passes of other radices keep the
 // workgroup kernel (their stores would be 16-byte pieces).
-// the conversions between the 16-byte elements of a pass's input / output and the five-limb form it computes in.  The experiments build
-// can replace them by register moves (-DGS_EXP_NO_FORMAT: results are garbage, TIMINGS are what a pass costs without them — the part
-// a plan with fewer passes would save one third of; tools/ntt_noformat.sh)
-#ifdef GS_EXP_NO_FORMAT
-__device__ __forceinline__ lz lz_unpack_fake(const fe &r) { lz x; x.l[0] = (int32_t)(r.w0 & LZ_M); x.l[1] = (int32_t)(r.w1 & LZ_M); x.l[2] = (int32_t)(r.w2 & LZ_M); x.l[3] = (int32_t)(r.w3 & LZ_M); x.l[4] = (int32_t)(r.w3 >> 26); return x; }
-__device__ __forceinline__ fe lz_pack_fake(const lz &x) { return fe_make((uint32_t)x.l[0], (uint32_t)x.l[1], (uint32_t)x.l[2], (uint32_t)(x.l[3] ^ (x.l[4] << 26))); }
-#define LZ_DATA_UNPACK(r) lz_unpack_fake(r)
-#define LZ_DATA_PACK(x, w) lz_pack_fake(x)
-#else
-#define LZ_DATA_UNPACK(r) lz_unpack(r)
-#define LZ_DATA_PACK(x, w) lz_pack_flag(x, w)
-#endif
+// The conversions between the 16-byte elements of a pass's input / output and the five-limb form it computes in cost 9 % of a
+// 2^24-point transform (round 4: 0.695 ms per transform against 0.629 with register moves in their place, results aside;
+// profiles/r04_l_ntt_without_format_conversions.txt) — the part a plan with fewer passes would save one third of.
 template <int LB, int TW>
 __global__ __launch_bounds__(64, 4) void k_ntt_wave(const fe *__restrict__ in, fe *__restrict__ out, LzPassArgs a) {
     constexpr int RB = 1 << LB, R = 16 * RB, GB = 16 / RB, LOGWJ = 6 - LB, Wj = 64 >> LB;
@@ -476,7 +430,7 @@ __global__ __launch_bounds__(64, 4) void k_ntt_wave(const fe *__restrict__ in, f
                     for (int u = 0; u < 4; u++) { tws[u] = *tp; tp += tstep; }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                v[m] = lz_mul_vm(LZ_DATA_UNPACK(raw[m]), lz_unpack(tws[m & 3]), K);
+                v[m] = lz_mul_vm(lz_unpack(raw[m]), lz_unpack(tws[m & 3]), K);
             }
             __builtin_amdgcn_sched_barrier(0);
         } else if constexpr (TW == 2) {
@@ -490,13 +444,13 @@ __global__ __launch_bounds__(64, 4) void k_ntt_wave(const fe *__restrict__ in, f
 #pragma unroll
             for (int m = 0; m < 16; m++) {
                 __builtin_amdgcn_sched_barrier(0);
-                v[m] = lz_mul_vm(LZ_DATA_UNPACK(raw[m]), cur, K);
+                v[m] = lz_mul_vm(lz_unpack(raw[m]), cur, K);
                 if (m < 15) cur = lz_mul_vm(cur, step, K);
             }
             __builtin_amdgcn_sched_barrier(0);
         } else {
 #pragma unroll
-            for (int m = 0; m < 16; m++) v[m] = LZ_DATA_UNPACK(raw[m]);
+            for (int m = 0; m < 16; m++) v[m] = lz_unpack(raw[m]);
         }
         ntt_dif_lz<4>(v, (lzw_cptr)a.wtab, K);
     }
@@ -534,7 +488,7 @@ __global__ __launch_bounds__(64, 4) void k_ntt_wave(const fe *__restrict__ in, f
         for (int q = 0; q < 16; q++) {
             lz x = v[brev(q, 4)];
             if (scale) { LZ_FENCE(); const lzw W = lz_load_w(wt + 7); x = lz_mul_u(lz_norm(x), W, K); }
-            dst[jbase + (uint64_t)q * Ns2] = LZ_DATA_PACK(x, weak);
+            dst[jbase + (uint64_t)q * Ns2] = lz_pack_flag(x, weak);
         }
     } else {
         // ---- exchange twiddles in place, then the exchange itself, limb plane by limb plane
@@ -571,7 +525,7 @@ __global__ __launch_bounds__(64, 4) void k_ntt_wave(const fe *__restrict__ in, f
             const uint64_t ostep = FIRST ? 16 : (Ns2 << 4);
 #pragma unroll
             for (int qb = 0; qb < RB; qb++) {
-                *o = LZ_DATA_PACK(xb[u][brev(qb, LB)], weak);
+                *o = lz_pack_flag(xb[u][brev(qb, LB)], weak);
                 o += ostep;
                 if ((qb & 3) == 3 || qb == RB - 1) __builtin_amdgcn_sched_barrier(0);
             }
@@ -595,7 +549,38 @@ __global__ void k_build_lz_table(const fe *__restrict__ src, lz8 *__restrict__ d
         dst[i] = o;
     }
 }
-#endif  // GS_NTT_LAZY
+#else
+// ======================================================================================================================
+// The pass kernel of the other field flavours, on canonical elements.
+
+// Fully unrolled decimation-in-frequency network on N = 2^LOGN registers.  w16[i] = omega_16^i.
+// Result is bit-reversed: X[q] = x[brev(q, LOGN)].
+template <int LOGN>
+__device__ __forceinline__ void ntt_dif_reg(fe (&x)[1 << LOGN], const fe (&w16)[8]) {
+    constexpr int N = 1 << LOGN;
+#pragma unroll
+    for (int s = N / 2; s >= 1; s >>= 1) {
+#pragma unroll
+        for (int b = 0; b < N; b += 2 * s) {
+#pragma unroll
+            for (int i = 0; i < s; i++) {
+                fe u = x[b + i], v = x[b + i + s];
+                x[b + i] = fe_add(u, v);
+                fe d = fe_sub(u, v);
+                const int tw = i * (N / 2 / s) * (16 / N);
+                x[b + i + s] = tw ? fe_mul(d, w16[tw]) : d;
+            }
+        }
+    }
+}
+
+struct PassArgs {
+    uint64_t n, in_len, in_stride, out_stride;
+    int logn, logNs, logWj, log_lo, scale;
+    const fe *tw_lo, *tw_hi, *wR, *twp;
+    fe w16[8];
+    fe ninv;
+};
 
 template <int LB>
 __global__ __launch_bounds__(256) void k_ntt_pass(const fe *__restrict__ in, fe *__restrict__ out, PassArgs a) {
@@ -707,6 +692,7 @@ __global__ __launch_bounds__(256) void k_ntt_pass(const fe *__restrict__ in, fe 
         tile[e] = lds[ej * (R + 1) + eq];
     }
 }
+#endif  // GS_FIELD_128
 
 // out[r][i] = scale * sum_c in[r][c] * (omega^i)^c  — short polynomials / tiny domains (Horner per point)
 __global__ void k_eval_horner(const fe *__restrict__ in, fe *__restrict__ out, uint64_t n, uint64_t in_len, uint64_t in_stride,
@@ -740,15 +726,7 @@ __global__ void k_scale_table(const fe *__restrict__ in, fe *__restrict__ out, u
 // inter-pass twiddle tables of up to 2^20 entries (16 MiB, L2 resident); larger passes keep the running product.  A [k][jq] table of
 // 2^24 entries for the third pass of a 2^24-point transform was measured (round 3): 0.697 ms against 0.670 ms per transform — the
 // table read costs what the saved chain products bring (profiles/r03_a_ntt_time_twiddle_log24.txt)
-static uint64_t max_pass_twiddle_entries() {
-#ifdef GS_NTT_EXPERIMENTS
-    static uint64_t v = 0;
-    if (!v) { const char *e = getenv("GSTARK_NTT_TWIDDLE_LOG"); v = 1ull << (e ? atoi(e) : 20); }
-    return v;
-#else
-    return 1ull << 20;
-#endif
-}
+static constexpr uint64_t kMaxPassTwiddleEntries = 1ull << 20;
 
 static std::string plan_key(const fe &omega, uint64_t n) {
     char buf[16 + 8 * GF_LIMBS + 24];
@@ -791,7 +769,7 @@ static int plan_get(gs_ctx *c, const fe &omega, uint64_t n, NttPlan **out) {
         p->npass = np;
         fe w16 = fe_pow_u64(omega, n / 16), cur = fe_one();
         for (int i = 0; i < 8; i++) { p->w16[i] = cur; cur = fe_mul(cur, w16); }
-#ifdef GS_NTT_LAZY
+#ifdef GS_FIELD_128
         {
             lzw host[8];
             for (int i = 1; i < 8; i++) lz_wform(p->w16[i], host[i - 1]);
@@ -804,8 +782,6 @@ static int plan_get(gs_ctx *c, const fe &omega, uint64_t n, NttPlan **out) {
                 return gs_fail(c, GS_ERR_DEVICE, "ntt: twiddle upload failed");
             }
         }
-#endif
-#ifdef GS_NTT_LAZY
         if ((rc = gs_alloc(c, (1ull << p->log_lo) * GS_ELT, &q))) { delete p; return rc; }
         p->tw_loR = (fe *)q;
         hipLaunchKernelGGL(k_scale_table, dim3(gs_grid(1ull << p->log_lo)), dim3(256), 0, c->stream, p->tw_lo, p->tw_loR, 1ull << p->log_lo, lz_mont_r());
@@ -814,19 +790,18 @@ static int plan_get(gs_ctx *c, const fe &omega, uint64_t n, NttPlan **out) {
         for (int i = 0; i < np; i++) {
             p->L[i] = base + (i < extra ? 1 : 0);
             uint64_t R = 1ull << p->L[i];
-            if (i > 0 && Ns_acc * R <= max_pass_twiddle_entries()) {
-#if !defined(GS_NTT_LAZY) || defined(GS_NTT_EXPERIMENTS)
-                if ((rc = gs_alloc(c, Ns_acc * R * GS_ELT, &q))) { delete p; return rc; }
-                p->twp[i] = (fe *)q;
-                hipLaunchKernelGGL(k_build_pass_twiddles, dim3(gs_grid(Ns_acc * R)), dim3(256), 0, c->stream, p->twp[i], Ns_acc, R,
-                                   n / (Ns_acc * R), p->tw_lo, p->tw_hi, p->log_lo, p->logn, fe_one(), 0);
-#endif
-#ifdef GS_NTT_LAZY
+            if (i > 0 && Ns_acc * R <= kMaxPassTwiddleEntries) {
+#ifdef GS_FIELD_128
                 // the lazy kernels multiply by these through lz_mul_vm (x * w * 2^-130): the table holds w * 2^130
                 if ((rc = gs_alloc(c, Ns_acc * R * GS_ELT, &q))) { delete p; return rc; }
                 p->twpR[i] = (fe *)q;
                 hipLaunchKernelGGL(k_build_pass_twiddles, dim3(gs_grid(Ns_acc * R)), dim3(256), 0, c->stream, p->twpR[i], Ns_acc, R,
                                    n / (Ns_acc * R), p->tw_lo, p->tw_hi, p->log_lo, p->logn, lz_mont_r(), 1);
+#else
+                if ((rc = gs_alloc(c, Ns_acc * R * GS_ELT, &q))) { delete p; return rc; }
+                p->twp[i] = (fe *)q;
+                hipLaunchKernelGGL(k_build_pass_twiddles, dim3(gs_grid(Ns_acc * R)), dim3(256), 0, c->stream, p->twp[i], Ns_acc, R,
+                                   n / (Ns_acc * R), p->tw_lo, p->tw_hi, p->log_lo, p->logn, fe_one(), 0);
 #endif
             }
             Ns_acc *= R;
@@ -839,7 +814,7 @@ static int plan_get(gs_ctx *c, const fe &omega, uint64_t n, NttPlan **out) {
                     p->wR[i] = (fe *)q;
                     if ((rc = gs_power_series_dev(c, fe_pow_u64(omega, n / R), R, p->wR[i]))) { delete p; return rc; }
                 }
-#ifdef GS_NTT_LAZY
+#ifdef GS_FIELD_128
                 for (int k = 0; k < i; k++)
                     if (p->L[k] == p->L[i]) p->wRz[i] = p->wRz[k];
                 if (!p->wRz[i]) {
@@ -925,22 +900,7 @@ int gs_plan_inverse_table_shifted(gs_ctx *c, const fe &omega, uint64_t n, const 
     return GS_OK;
 }
 
-template <int LB>
-static void launch_pass(gs_ctx *c, const fe *in, fe *out, const PassArgs &a, uint32_t rows) {
-    constexpr int RB = 1 << LB, R = 16 * RB;
-    const int Wj = 1 << a.logWj;
-    const uint64_t tiles = (a.n / R) / Wj;
-    const bool need_lds = (RB > 1) || (a.logNs == 0);
-    const size_t lds = need_lds ? (size_t)Wj * (R + 1) * GS_ELT : 0;
-    // the attribute is per device and the library may serve several contexts / devices from several threads: no process-wide
-    // "already set" flag; only tiles above the 64 KiB default need it (the multi-limb flavours)
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ntt_pass<LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(k_ntt_pass<LB>, dim3((unsigned)tiles, rows), dim3(RB * Wj), lds, c->stream, in, out, a);
-}
-
-
-#ifdef GS_NTT_LAZY
+#ifdef GS_FIELD_128
 template <int LB>
 static void launch_pass_lz(gs_ctx *c, const fe *in, fe *out, const LzPassArgs &a, uint32_t rows) {
     constexpr int RB = 1 << LB, R = 16 * RB;
@@ -967,39 +927,20 @@ static void launch_pass_wave(gs_ctx *c, const fe *in, fe *out, const LzPassArgs 
     } else if (a.twp) hipLaunchKernelGGL((k_ntt_wave<LB, 1>), dim3((unsigned)tiles, rows), dim3(64), 0, c->stream, in, out, a);
     else hipLaunchKernelGGL((k_ntt_wave<LB, 2>), dim3((unsigned)tiles, rows), dim3(64), 0, c->stream, in, out, a);
 }
-// ---- A/B variants measured in rounds 1-2 and NOT adopted: compiled only into the experiments library
-// (tools/build_experiments.sh -> tools/ab/libgstark_hip_exp.so, -DGS_NTT_EXPERIMENTS), where environment switches select them
-// per call.  The product library contains one kernel family per field flavour and reads no environment variable here.
-#ifdef GS_NTT_EXPERIMENTS
-#include "../../tools/ntt_mfma.h"
-__global__ void k_mf_scale_table(const fe *__restrict__ in, fe *__restrict__ out, fe k) { out[threadIdx.x] = fe_mul(in[threadIdx.x], k); }
-static void launch_pass_mfma(gs_ctx *c, const fe *in, fe *out, const MfPassArgs &a, uint32_t rows) {
-    const uint64_t tiles = (a.n >> 8) / MF_COLS;
-    static_assert(MF_LDS_BYTES <= 64 * 1024, "below the default dynamic LDS limit: no attribute needed");
-    const dim3 grid((unsigned)(tiles / MF_WAVES), rows), block(64 * MF_WAVES);
-    if (a.logNs == 0) hipLaunchKernelGGL((k_ntt_mfma<0>), grid, block, MF_LDS_BYTES, c->stream, in, out, a);
-    else if (a.twp) hipLaunchKernelGGL((k_ntt_mfma<1>), grid, block, MF_LDS_BYTES, c->stream, in, out, a);
-    else hipLaunchKernelGGL((k_ntt_mfma<2>), grid, block, MF_LDS_BYTES, c->stream, in, out, a);
-}
-static bool ntt_mfma_enabled() {   // GSTARK_NTT_MFMA=1: radix-256 passes on the matrix cores (A/B measurements; read per call)
-    const char *e = getenv("GSTARK_NTT_MFMA");
-    return e && e[0] == '1';
-}
-
-static bool ntt_wave_enabled() {   // GSTARK_NTT_WAVE=0 keeps the 128-thread workgroup kernel everywhere (A/B measurements)
-    const char *e = getenv("GSTARK_NTT_WAVE");
-    return !(e && e[0] == '0');
-}
-
-static bool ntt_lazy_enabled() {   // GSTARK_NTT_LAZY=0 keeps the canonical-limb kernel (A/B measurements)
-    const char *e = getenv("GSTARK_NTT_LAZY");   // read per call: tools/ntt_ab.py flips it inside one process
-    return !(e && e[0] == '0');
-}
 #else
-static constexpr bool ntt_mfma_enabled() { return false; }
-static constexpr bool ntt_wave_enabled() { return true; }
-static constexpr bool ntt_lazy_enabled() { return true; }
-#endif  // GS_NTT_EXPERIMENTS
+template <int LB>
+static void launch_pass(gs_ctx *c, const fe *in, fe *out, const PassArgs &a, uint32_t rows) {
+    constexpr int RB = 1 << LB, R = 16 * RB;
+    const int Wj = 1 << a.logWj;
+    const uint64_t tiles = (a.n / R) / Wj;
+    const bool need_lds = (RB > 1) || (a.logNs == 0);
+    const size_t lds = need_lds ? (size_t)Wj * (R + 1) * GS_ELT : 0;
+    // the attribute is per device and the library may serve several contexts / devices from several threads: no process-wide
+    // "already set" flag; only tiles above the 64 KiB default need it (the multi-limb flavours)
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ntt_pass<LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(k_ntt_pass<LB>, dim3((unsigned)tiles, rows), dim3(RB * Wj), lds, c->stream, in, out, a);
+}
 #endif
 
 // rows transforms of size n; row r reads in[r*in_stride .. +in_len) (zero-extended) and writes out[r*n .. +n)
@@ -1045,84 +986,51 @@ static int ntt_run(gs_ctx *c, const fe *in, uint32_t rows, uint64_t in_len, uint
         const int LB = p->L[i] - 4;
         const uint64_t R = 1ull << p->L[i];
         const bool last = (i == p->npass - 1);
-#ifdef GS_NTT_LAZY
-        if (ntt_lazy_enabled()) {
-            LzPassArgs a;
-            a.n = n;
-            a.in_len = (i == 0) ? in_len : n;
-            a.in_stride = (i == 0) ? in_stride : n;
-            a.out_stride = n;
-            a.logn = p->logn;
-            a.logNs = logNs;
-            uint64_t Wj = 128 >> LB;
-            if (Wj > n / R) Wj = n / R;
-            a.logWj = gs_log2(Wj);
-            a.log_lo = p->log_lo;
-            a.tw_lo = p->tw_lo;
-            a.tw_hi = p->tw_hi;
-            a.twp = p->twpR[i];
-            a.tw_loR = p->tw_loR;
-            a.wR = p->wRz[i];
-            a.scale = 0;
-            a.exq0 = 0;
-            a.weak = last ? 0 : 1;
-            if (inverse && last) {
-                if (LB > 0) {   // the 1/n scale rides on the exchange twiddles of the last pass
-                    if (!p->wRz_scaled) {
-                        void *q;
-                        if ((rc = gs_alloc(c, R * sizeof(lz8), &q))) { if (tmp) gs_tmp_free(c, tmp); return rc; }
-                        p->wRz_scaled = (lz8 *)q;
-                        hipLaunchKernelGGL(k_build_lz_table, dim3(gs_grid(R)), dim3(256), 0, c->stream, p->wR[i], p->wRz_scaled, R, fe_mul(ninv, lz_mont_r()), 1);
-                    }
-                    a.wR = p->wRz_scaled;
-                    a.exq0 = 1;
-                } else {
-                    a.scale = 1;
-                }
-            }
-            a.wtab = p->wtab;
-            const bool wave = ntt_wave_enabled() && n >= 1024 && (logNs > 0 || LB == 4);
-#ifdef GS_NTT_EXPERIMENTS
-            if (LB == 4 && n >= (1ull << 16) && ntt_mfma_enabled()) {
-                if (!p->mf_tab) {
-                    int8_t host[4096];
-                    mf_host_tables(p->w16[1], host, p->mf_offs, p->mf_bias0);
+#ifdef GS_FIELD_128
+        LzPassArgs a;
+        a.n = n;
+        a.in_len = (i == 0) ? in_len : n;
+        a.in_stride = (i == 0) ? in_stride : n;
+        a.out_stride = n;
+        a.logn = p->logn;
+        a.logNs = logNs;
+        uint64_t Wj = 128 >> LB;
+        if (Wj > n / R) Wj = n / R;
+        a.logWj = gs_log2(Wj);
+        a.log_lo = p->log_lo;
+        a.tw_lo = p->tw_lo;
+        a.tw_hi = p->tw_hi;
+        a.twp = p->twpR[i];
+        a.tw_loR = p->tw_loR;
+        a.wR = p->wRz[i];
+        a.scale = 0;
+        a.exq0 = 0;
+        a.weak = last ? 0 : 1;
+        if (inverse && last) {
+            if (LB > 0) {   // the 1/n scale rides on the exchange twiddles of the last pass
+                if (!p->wRz_scaled) {
                     void *q;
-                    if ((rc = gs_alloc(c, sizeof host, &q))) { if (tmp) gs_tmp_free(c, tmp); return rc; }
-                    if (hipMemcpyAsync(q, host, sizeof host, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-                        if (tmp) gs_tmp_free(c, tmp);
-                        return gs_fail(c, GS_ERR_DEVICE, "ntt: operand table upload failed");
-                    }
-                    p->mf_tab = (int4 *)q;
+                    if ((rc = gs_alloc(c, R * sizeof(lz8), &q))) { if (tmp) gs_tmp_free(c, tmp); return rc; }
+                    p->wRz_scaled = (lz8 *)q;
+                    hipLaunchKernelGGL(k_build_lz_table, dim3(gs_grid(R)), dim3(256), 0, c->stream, p->wR[i], p->wRz_scaled, R, fe_mul(ninv, lz_mont_r()), 1);
                 }
-                MfPassArgs m;
-                m.n = n; m.in_len = a.in_len; m.in_stride = a.in_stride; m.out_stride = n;
-                m.logn = p->logn; m.logNs = logNs; m.log_lo = p->log_lo; m.weak = last ? 0 : 1;
-                m.tw_lo = p->tw_lo; m.tw_hi = p->tw_hi; m.twp = p->twp[i]; m.wR = p->wR[i]; m.atab = p->mf_tab;
-                for (int k = 0; k < 16; k++) m.offs[k] = p->mf_offs[k];
-                m.bias0 = p->mf_bias0;
-                if (inverse && last) {
-                    if (!p->mf_wR_scaled) {
-                        void *q;
-                        if ((rc = gs_alloc(c, 256 * GS_ELT, &q))) { if (tmp) gs_tmp_free(c, tmp); return rc; }
-                        p->mf_wR_scaled = (fe *)q;
-                        hipLaunchKernelGGL(k_mf_scale_table, dim3(1), dim3(256), 0, c->stream, p->wR[i], p->mf_wR_scaled, ninv);
-                    }
-                    m.wR = p->mf_wR_scaled;
-                }
-                launch_pass_mfma(c, src, dst, m, rows);
-            } else
-#endif
-            if (wave) {
-                a.logWj = 6 - LB;
-                switch (LB) {
-                    case 0: launch_pass_wave<0>(c, src, dst, a, rows); break;
-                    case 1: launch_pass_wave<1>(c, src, dst, a, rows); break;
-                    case 2: launch_pass_wave<2>(c, src, dst, a, rows); break;
-                    case 3: launch_pass_wave<3>(c, src, dst, a, rows); break;
-                    default: launch_pass_wave<4>(c, src, dst, a, rows); break;
-                }
-            } else
+                a.wR = p->wRz_scaled;
+                a.exq0 = 1;
+            } else {
+                a.scale = 1;
+            }
+        }
+        a.wtab = p->wtab;
+        if (n >= 1024 && (logNs > 0 || LB == 4)) {   // k_ntt_wave; first passes below radix 256 and transforms below 1024 points: k_ntt_pass_lz
+            a.logWj = 6 - LB;
+            switch (LB) {
+                case 0: launch_pass_wave<0>(c, src, dst, a, rows); break;
+                case 1: launch_pass_wave<1>(c, src, dst, a, rows); break;
+                case 2: launch_pass_wave<2>(c, src, dst, a, rows); break;
+                case 3: launch_pass_wave<3>(c, src, dst, a, rows); break;
+                default: launch_pass_wave<4>(c, src, dst, a, rows); break;
+            }
+        } else {
             switch (LB) {
                 case 0: launch_pass_lz<0>(c, src, dst, a, rows); break;
                 case 1: launch_pass_lz<1>(c, src, dst, a, rows); break;
@@ -1130,9 +1038,8 @@ static int ntt_run(gs_ctx *c, const fe *in, uint32_t rows, uint64_t in_len, uint
                 case 3: launch_pass_lz<3>(c, src, dst, a, rows); break;
                 default: launch_pass_lz<4>(c, src, dst, a, rows); break;
             }
-        } else
-#endif
-        {
+        }
+#else
         PassArgs a;
         a.n = n;
         a.in_len = (i == 0) ? in_len : n;
@@ -1158,7 +1065,7 @@ static int ntt_run(gs_ctx *c, const fe *in, uint32_t rows, uint64_t in_len, uint
             case 3: launch_pass<3>(c, src, dst, a, rows); break;
             default: launch_pass<4>(c, src, dst, a, rows); break;
         }
-        }
+#endif
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             if (tmp) gs_tmp_free(c, tmp);

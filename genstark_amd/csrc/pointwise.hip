@@ -78,7 +78,7 @@ __device__ __forceinline__ fe fe_shfl(const fe &v, int lane) {
     return o;
 }
 
-#if !defined(GS_SMALL_Q) && !defined(GS_WIDE_BITS)
+#ifdef GS_FIELD_128
 #include "gf128_lazy.h"
 // a^(p-2) on ONE lane while the rest of the workgroup waits: 127 squarings + 12 products, all dependent.  In the lazy five-limb form a
 // squaring is ~53 instructions instead of 84 (gf128_lazy.h: lz_sqr), and on a lone wave the chain costs its instruction count.
@@ -231,8 +231,7 @@ __global__ void k_div_by_domain_roots(const fe *__restrict__ num, const fe *__re
 // scalar loads.  Each quotient's constant prod_a w^-r_a is folded into its two coefficients on the host.
 #define GS_TAIL_MAX_ROOTS 4
 #define GS_TAIL_MAX_ILEN 4
-#if !defined(GS_SMALL_Q) && !defined(GS_WIDE_BITS)
-#define GS_TAIL_LAZY 1
+#ifdef GS_FIELD_128
 // 128-bit field: both sums are dot products with UNIFORM constants — sum_t k_t x_t and sum_t k'_t x_t over the boundary quotients and
 // the committed vectors alike, l = D + S + pw * S'.  A term is one lz_unpack of x_t and 2 x 25 v_mad into two sets of nine 64-bit
 // columns (the constants' limbs, unpacked on the host, arrive through scalar loads); a set is folded every six terms (columns below
@@ -243,7 +242,7 @@ struct TailK { fe k, kp; };
 #endif
 struct TailRow { const fe *v; uint64_t root[GS_TAIL_MAX_ROOTS]; fe ipoly[GS_TAIL_MAX_ILEN]; TailK c; uint32_t nroots, pad[3]; };
 struct TailVec { const fe *v; uint64_t pad; TailK c; };
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
 struct TailSums {
     int64_t a[9], b[9];
     fe pa, pb;
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(256) void k_composition_tail(const fe *__restrict__
                                                           uint64_t pw_exp, fe pw_step, fe shift, fe pw_scale, int has_shift, fe *__restrict__ c_out,
                                                           fe *__restrict__ l_out) {
     static_assert(!ZC || HAS_X, "1/Z(x) needs x");
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
     const lzk K = lzk_make();
 #endif
     __shared__ fe zc[GS_ZPOLY_MAX_PERIOD];
@@ -315,7 +314,7 @@ __global__ __launch_bounds__(256) void k_composition_tail(const fe *__restrict__
             if (has_shift) x = fe_mul(x, shift);                     // (wave-uniform flag)
         }
         const fe d = fe_mul(q[i], ZC ? fe_mul(fe_sub(x, x_last), zc[i & (period - 1)]) : zinv[i]);
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
         TailSums s;
 #pragma unroll
         for (int k = 0; k < 9; k++) { s.a[k] = 0; s.b[k] = 0; }
@@ -331,14 +330,14 @@ __global__ __launch_bounds__(256) void k_composition_tail(const fe *__restrict__
             if (HAS_X) for (int t = (int)ilen - 2; t >= 0; t--) iv = fe_add(fe_mul(iv, x), r.ipoly[t]);
             fe t = fe_sub(r.v[i], iv);
             for (uint32_t a = 0; a < r.nroots; a++) t = fe_mul(t, u[(i + n - r.root[a]) & (n - 1)]);
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
             tail_term<HAS_PW>(s, t, r.c, K);
 #else
             const fe cf = HAS_PW ? fe_add(r.c.k, fe_mul(p, r.c.kp)) : r.c.k;
             acc = fe_add(acc, fe_mul(t, cf));
 #endif
         }
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
         if (c_out) {
             if (s.terms) tail_flush<HAS_PW>(s, K);
             c_out[i] = HAS_PW ? fe_add(s.pa, fe_mul(p, s.pb)) : s.pa;
@@ -356,7 +355,7 @@ __global__ __launch_bounds__(256) void k_composition_tail(const fe *__restrict__
             for (int k = 0; k < 6; k++) {
                 if (v0 + k >= lcount) break;
                 const TailVec &e = vecs[v0 + k];
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
                 tail_term<HAS_PW>(s, xs[k], e.c, K);
 #else
                 const fe cf = HAS_PW ? fe_add(e.c.k, fe_mul(p, e.c.kp)) : e.c.k;
@@ -364,7 +363,7 @@ __global__ __launch_bounds__(256) void k_composition_tail(const fe *__restrict__
 #endif
             }
         }
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
         if (s.terms) tail_flush<HAS_PW>(s, K);
         l_out[i] = HAS_PW ? fe_add(s.pa, fe_mul(p, s.pb)) : s.pa;
 #else
@@ -786,7 +785,7 @@ int gs_div_by_domain_roots_coset(gs_ctx *c, const void *num, uint32_t rows, uint
 }
 
 static void tail_coeffs(TailK &c, const fe &k, const fe &kp) {
-#ifdef GS_TAIL_LAZY
+#ifdef GS_FIELD_128
     const lz a = lz_unpack(k), b = lz_unpack(kp);
     for (int i = 0; i < 5; i++) { c.k[i] = a.l[i]; c.kp[i] = b.l[i]; }
 #else

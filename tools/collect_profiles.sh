@@ -9,8 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 # 1. instruction costs and arithmetic cores (the second roof)
 $R/tools/microbench4 > $O/${TAG}_a_instruction_costs.txt 2>&1
 $R/tools/microbench5 > $O/${TAG}_a_arithmetic_cores.txt 2>&1
-# 2. NTT kernels: A/B against the canonical-limb kernel, per-kernel trace, SQ counters, HBM traffic
-python $R/tools/ntt_ab.py 24 > $O/${TAG}_b_ntt_ab.txt 2>&1
+# 2. NTT kernels: per-kernel trace, SQ counters, HBM traffic
 rocprofv3 --kernel-trace --stats -d $O/trace_ntt -o t -- python $R/tools/ntt_only.py 24 > /dev/null 2>&1
 python $R/tools/rocprof_summary.py $O/trace_ntt/t_results.db rocprofv3 --kernel-trace --stats -- python tools/ntt_only.py 24 > $O/${TAG}_c_kernel_stats_ntt_2p24.md 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/pmc_sq -o s -- python $R/tools/ntt_only.py 24 > /dev/null 2>&1
