@@ -129,6 +129,14 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# include/gstark_boundary.h: entry points an implementation of the ABI may lack (the HIP library has them, the tests' double does not);
+# bound where present, and a caller that needs one asks `hasattr(lib, name)` first
+_OPTIONAL_SIGNATURES = {
+    'gs_boundary_polys': (_int, [_vp, _bytes, _u64, _u64, C.POINTER(_u64), _bytes, C.POINTER(_u32), _u32, _u32, _vp, _vp]),
+    'gs_boundary_schoolbook_log2': (_u32, [_u32]),
+}
+OPTIONAL_SYMBOLS = tuple(_OPTIONAL_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -143,6 +151,10 @@ def load_library(path):
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
+    for name, (res, args) in _OPTIONAL_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
     return lib
 
 

@@ -25,6 +25,7 @@
 #include "../../include/gstark.h"
 #include "../../include/gstark_prover.h"
 #include "../../include/gstark_comm.h"
+#include "../../include/gstark_boundary.h"
 // One build of this file per field flavour of the ABI library (csrc/build.sh: the same -DGS_SMALL_Q / -DGS_WIDE_BITS): the host-side
 // scalars (domain roots, Fiat-Shamir coefficients, boundary interpolants, the remainder check) use the flavour's host arithmetic,
 // elements are gs_element_size() bytes on the ABI and in the proof.
@@ -45,9 +46,12 @@ namespace {
     X(gs_small_eval_poly) X(gs_pseudorandom_indexes) X(gs_mimc_trace) X(gs_mimc_constraints) X(gs_air_trace)                    \
     X(gs_air_trace_segments) X(gs_air_constraints) X(gs_air_constraints_strided) X(gs_composition_tail) X(gs_composition_tail_coset) X(gs_zero_poly_inverses) X(gs_div_by_domain_roots) X(gs_mimc_composition) X(gs_fri_fold) X(gs_fri_fold_seeded) X(gs_defer_begin) X(gs_defer_end) X(gs_readback_post) X(gs_readback_wait) X(gs_merkle_commit_rows_seed) X(gs_fri_fold_at) \
     X(gs_vec_mul_scalar) X(gs_copy) X(gs_gather_words) X(gs_transpose_records) X(gs_fri_fold_seeded_scaled) X(gs_fri_layers) X(gs_sync) X(gs_zero_poly_inverses_coset) X(gs_div_by_domain_roots_coset)
+// ... and the entry points an implementation may lack (include/gstark_boundary.h): null then, and the driver keeps its host path
+#define GS_API_OPTIONAL_LIST(X) X(gs_boundary_polys)
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
     GS_API_LIST(X)
+    GS_API_OPTIONAL_LIST(X)
 #undef X
 };
 // The driver is written against `A.gs_xxx(...)`: A is the binding of the CURRENT call on this thread — the process-wide default
@@ -429,6 +433,7 @@ int prove_guarded(gs_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *len, char *
 static thread_local gs_prover_stats g_stats;
 static thread_local bool g_sync_phases = false;      // gs_prover_sync_phases
 static thread_local bool g_member_sequence = false;  // gs_prover_member_sequence
+static thread_local bool g_host_boundary = false;    // gs_prover_host_boundary
 // gs_composition_tail[_coset] takes up to four assertions per register, 64 asserted registers, 96 committed vectors
 static bool tail_fits(const gs_prover_job &job, uint32_t vectors) {
     if (g_member_sequence || vectors > 96) return false;
@@ -463,6 +468,9 @@ static int bind_api(Api &api, void *dl_handle) {
     api.name = (decltype(api.name))dlsym(dl_handle, #name);     \
     if (!api.name) return GS_ERR_UNSUPPORTED;
     GS_API_LIST(X)
+#undef X
+#define X(name) api.name = (decltype(api.name))dlsym(dl_handle, #name);
+    GS_API_OPTIONAL_LIST(X)
 #undef X
     // the library must compute in the field this build of the driver does its host-side scalars in
     auto esize = (int (*)())dlsym(dl_handle, "gs_element_size");
@@ -543,6 +551,7 @@ static int remainder_check_entry(const uint8_t *values, uint64_t len, uint32_t e
 
 void gs_prover_sync_phases(int on) { g_sync_phases = on != 0; }
 void gs_prover_member_sequence(int on) { g_member_sequence = on != 0; }
+void gs_prover_host_boundary(int on) { g_host_boundary = on != 0; }
 
 int gs_prover_abi_version(void) { return GS_PROVER_ABI_VERSION; }
 
@@ -731,8 +740,27 @@ struct Plan {
     uint64_t cf, Nc, combination_degree, composition_degree, b_inc;     // CompositionPolynomial.ts:196-204
     uint32_t exe_query_count, fri_query_count;
     // boundary constraints per asserted register, in order of first appearance (BoundaryConstraints.ts:15-45)
+    // (xs: the assertions' points omega^(step E) — what the host-side interpolation works on; make_plan leaves them to fill_xs on request)
     struct Reg { uint32_t reg; std::vector<uint64_t> steps; std::vector<F> xs, ys; };
     std::vector<Reg> regs;
+    void fill_xs() {
+        size_t total = 0;
+        for (auto &r : regs) total += r.steps.size();
+        // an exponentiation per assertion, or — many assertions — the execution domain's points once (T products) and look-ups
+        std::vector<F> table;
+        if (total * 32 > T) {
+            table.resize(T);
+            const F g = hf_pow(omega, (hfe)E);
+            F cur = 1;
+            for (uint64_t j = 0; j < T; j++) { table[j] = cur; cur = hf_mul(cur, g); }
+        }
+        for (auto &r : regs) {
+            r.xs.resize(r.steps.size());
+            for (size_t k = 0; k < r.steps.size(); k++)
+                r.xs[k] = !table.empty() && r.steps[k] < T ? table[r.steps[k]] : hf_pow(omega, (hfe)(r.steps[k] * E));
+        }
+    }
+
     // constraints grouped by degree (times T), in order of first appearance (CompositionPolynomial.ts:206-225)
     std::vector<std::pair<uint64_t, std::vector<uint32_t>>> groups;
     uint32_t dcount, bcoef;                              // coefficients of Q's terms, of the boundary terms
@@ -795,7 +823,7 @@ struct Plan {
     }
 };
 // the trace of T steps at extension factor E, omega of order T E
-Plan make_plan(const gs_prover_job &job, uint64_t T, uint64_t E, F omega) {
+Plan make_plan(const gs_prover_job &job, uint64_t T, uint64_t E, F omega, bool with_xs = true) {
     const gs_prover_air &air = job.air;
     Plan p;
     p.T = T; p.E = E; p.N = T * E; p.omega = omega;
@@ -806,15 +834,22 @@ Plan make_plan(const gs_prover_job &job, uint64_t T, uint64_t E, F omega) {
     p.b_inc = p.composition_degree - T;
     p.exe_query_count = job.exe_query_count;
     p.fri_query_count = job.fri_query_count;
+    std::vector<int32_t> slot(air.registers, -1);             // register -> its entry of p.regs (a statement may assert thousands of cells)
     for (uint32_t i = 0; i < job.nassertions; i++) {
         const gs_assertion &a = job.assertions[i];
-        Plan::Reg *r = nullptr;
-        for (auto &e : p.regs) if (e.reg == a.reg) r = &e;
-        if (!r) { p.regs.push_back(Plan::Reg{a.reg, {}, {}, {}}); r = &p.regs.back(); }
-        r->steps.push_back(a.step);
-        r->xs.push_back(hf_pow(omega, (hfe)(a.step * E)));
-        r->ys.push_back(from16(a.value));
+        int32_t at = -1;
+        if (a.reg < slot.size()) at = slot[a.reg];
+        else for (size_t k = 0; k < p.regs.size(); k++) if (p.regs[k].reg == a.reg) at = (int32_t)k;      // (out of range: refused by the caller)
+        if (at < 0) {
+            at = (int32_t)p.regs.size();
+            p.regs.push_back(Plan::Reg{a.reg, {}, {}, {}});
+            if (a.reg < slot.size()) slot[a.reg] = at;
+        }
+        Plan::Reg &r = p.regs[at];
+        r.steps.push_back(a.step);
+        r.ys.push_back(from16(a.value));
     }
+    if (with_xs) p.fill_xs();
     for (uint32_t i = 0; i < air.nconstraints; i++) {
         const uint64_t d = (uint64_t)air.degrees[i] * T;
         bool found = false;
@@ -897,7 +932,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     const Shapes input_shapes = checked_job_shapes(job);          // iShapes of the proof (lib/Stark.ts:161); empty without input registers
     if (E < 2 * composition_factor(air)) fail(GS_ERR_ARG, "extension factor must be at least 2x the composition factor");
     const F omega = domain_root(job, N);
-    const Plan plan = make_plan(job, T, E, omega);
+    Plan plan = make_plan(job, T, E, omega, false);
     const uint64_t Nc = plan.Nc, combination_degree = plan.combination_degree, b_inc = plan.b_inc;
     const F comp_rou = hf_pow(omega, (hfe)(N / Nc)), exec_rou = hf_pow(omega, (hfe)E);
     uint8_t s16[ELEM], s16b[ELEM];
@@ -916,6 +951,16 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     // the power series of the degree adjustment is materialised then
     const bool tail = !fused && tail_fits(job, R + air.nsecret);
     const bool tail_makes_z = tail && E <= 32;
+    // registers with many assertions: I_r and Z_r are built on the device (gs_boundary_polys) where the bound
+    // library has that entry point — otherwise, and for the few assertions of every other statement, on this host core
+    uint32_t most_assertions = 0;
+    for (auto &r : plan.regs) most_assertions = std::max(most_assertions, (uint32_t)r.steps.size());
+    // (the device path costs a fixed ~0.3 ms of transforms and launches whatever the count; measured, profiles/boundary_polys.md: at 128
+    //  assertions on a register the host path is still ahead — 1.44 vs 1.53 ms at 2^13 steps, 5.09 vs 5.23 at 2^16 —, at 256 it is behind)
+    const uint32_t DEVICE_BOUNDARY_ABOVE = 128;
+    const bool device_boundary = !fused && !tail && most_assertions > DEVICE_BOUNDARY_ABOVE && A.gs_boundary_polys && !g_host_boundary && plan.regs.size() <= 64 &&
+                                 most_assertions <= T && T <= (1ull << 28);
+    if (!device_boundary) plan.fill_xs();
     Buf zInverses;
     if (!fused && !tail_makes_z) {
         zInverses = Buf(x, N * ELEM);
@@ -1096,7 +1141,8 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         x.check(A.gs_vec_mul(x.c, qe.p, zInverses.p, N, dEval.p), "gs_vec_mul(D)");
         // 5.5 boundary constraints (BoundaryConstraints.ts:71-95)
         std::vector<std::vector<F>> ipolys, zpolys;
-        for (auto &r : plan.regs) { ipolys.push_back(lagrange(r.xs, r.ys)); zpolys.push_back(plan.zero_poly(r)); }
+        if (!device_boundary)
+            for (auto &r : plan.regs) { ipolys.push_back(lagrange(r.xs, r.ys)); zpolys.push_back(plan.zero_poly(r)); }
         auto upload_rows = [&](const std::vector<std::vector<F>> &rows, size_t len) {
             Bytes host(rows.size() * len * ELEM, 0);                    // shorter rows are zero-extended (newMatrixFromVectors)
             for (size_t r = 0; r < rows.size(); r++)
@@ -1107,7 +1153,22 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         };
         const Plan::Boundary bd = plan.boundary(E, false);
         const uint32_t ilen = bd.width, zlen = bd.width + 1;              // m assertions: m interpolant coefficients, m + 1 of Z_r
-        Buf iPolys = upload_rows(ipolys, ilen);
+        Buf iPolys, zPolys;
+        if (device_boundary) {
+            iPolys = Buf(x, (uint64_t)bcount * ilen * ELEM);
+            zPolys = Buf(x, (uint64_t)bcount * zlen * ELEM);
+            std::vector<uint64_t> at((size_t)bcount * bd.width, 0);
+            Bytes ys((size_t)bcount * bd.width * ELEM, 0);
+            for (uint32_t r = 0; r < bcount; r++)
+                for (size_t k = 0; k < plan.regs[r].steps.size(); k++) {
+                    at[(size_t)r * bd.width + k] = plan.regs[r].steps[k];
+                    le16(plan.regs[r].ys[k], ys.data() + ((size_t)r * bd.width + k) * ELEM);
+                }
+            le16(omega, s16);
+            x.check(A.gs_boundary_polys(x.c, s16, N, T, at.data(), ys.data(), bd.per_row.data(), bcount, bd.width, iPolys.p, zPolys.p), "gs_boundary_polys");
+        } else {
+            iPolys = upload_rows(ipolys, ilen);
+        }
         Buf iValues(x, (uint64_t)bcount * N * ELEM), pi(x, (uint64_t)bcount * N * ELEM), bEval(x, (uint64_t)bcount * N * ELEM);
         le16(omega, s16);
         x.check(counted_eval_polys_at_roots(x.c, iPolys.p, bcount, ilen, s16, N, iValues.p), "gs_eval_polys_at_roots(I)");
@@ -1117,7 +1178,8 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
             // and inverting it (same values: BoundaryConstraints.ts:88,92)
             x.check(A.gs_div_by_domain_roots(x.c, pi.p, bcount, N, s16, bd.at.data(), bd.per_row.data(), bd.width, bEval.p), "gs_div_by_domain_roots");
         } else {
-            Buf zPolys = upload_rows(zpolys, zlen), zValues(x, (uint64_t)bcount * N * ELEM);
+            if (!device_boundary) zPolys = upload_rows(zpolys, zlen);
+            Buf zValues(x, (uint64_t)bcount * N * ELEM);
             x.check(counted_eval_polys_at_roots(x.c, zPolys.p, bcount, zlen, s16, N, zValues.p), "gs_eval_polys_at_roots(Zb)");
             x.check(A.gs_vec_div(x.c, pi.p, zValues.p, (uint64_t)bcount * N, bEval.p), "gs_vec_div(B)");
         }

@@ -290,6 +290,124 @@ void rotate_column(std::vector<F> &col, int32_t shift) {
     std::rotate(col.begin(), col.begin() + k, col.end());
 }
 
+// ---- boundary constraints at the queried points (BoundaryConstraints.ts:55-69): I_r(x) and Z_r(x) of one asserted register
+// The reference's form — interpolate the m assertions, multiply the m factors out, evaluate both (lagrange + Plan::zero_poly + Horner) —
+// costs ~3 m^2 products and gs_small_interpolate stops at 4096 points.  For a register with many assertions the same VALUES come from
+//   Z_r          a product tree over the factors (schoolbook below, the host transform above BOUNDARY_SCHOOLBOOK_MAX coefficients),
+//   c_i          = y_i / Z_r'(x_i): Z_r' over the whole execution domain is ONE T-point transform (the x_i are points of it),
+//   I_r(x)       = Z_r(x) sum_i c_i / (x - x_i)  at each queried x (none of them lies in the execution domain): O(m) per point.
+// m comes from the statement's assertions.  T is the statement's too, except for an AIR with input registers verified with job.steps = 0:
+// there the proof's shapes lay the trace out (capped at 2^26 steps above), and this form then allocates two T-long vectors like the
+// input-register columns do.
+// in place: a[j] <- sum_i a[i] w^(i j), w of order a.size() (a power of two)
+void host_transform(std::vector<F> &a, F w) {
+    const size_t n = a.size();
+    uint32_t lg = 0;
+    while (((size_t)1 << lg) < n) lg++;
+    for (size_t i = 0; i < n; i++) {
+        size_t r = 0;
+        for (uint32_t b = 0; b < lg; b++) r |= ((i >> b) & 1) << (lg - 1 - b);
+        if (i < r) std::swap(a[i], a[r]);
+    }
+    std::vector<F> tw(n / 2 ? n / 2 : 1);
+    F cur = 1;
+    for (size_t k = 0; k < n / 2; k++) { tw[k] = cur; cur = hf_mul(cur, w); }
+    for (size_t half = 1; half < n; half <<= 1) {
+        const size_t stride = n / (2 * half);
+        for (size_t base = 0; base < n; base += 2 * half)
+            for (size_t k = 0; k < half; k++) {
+                const F u = a[base + k], v = vf_mul(a[base + k + half], tw[k * stride]);
+                a[base + k] = hf_add(u, v);
+                a[base + k + half] = hf_sub(u, v);
+            }
+    }
+}
+// Products with an operand of at most this many coefficients are schoolbook products.  Chosen by count, not measured on its own: 64 x 64
+// is 4 096 products, the three 128-point transforms it would replace ~1 350 butterflies plus their set-up, and below it the
+// transforms' bit reversal and twiddle tables outweigh the difference.
+const size_t BOUNDARY_SCHOOLBOOK_MAX = 64;
+// Registers with at most this many assertions keep the reference's form.  Measured with tools/boundary_host_bench.py (one core, 128-bit
+// flavour, T = 2^13, 128 queried points; direct / tree in ms): m = 64: 1.1 / 4.4, 128: 3.1 / 5.6, 256: 8.8 / 8.7, 1 024: 112 / 30,
+// 4 096: 1 387 / 102.  The tree form's floor is its T-point transform; the two cross at m = 256.
+const size_t BOUNDARY_DIRECT_MAX = 256;
+std::vector<F> poly_product(const std::vector<F> &a, const std::vector<F> &b, F omega, uint64_t N) {
+    const size_t len = a.size() + b.size() - 1;
+    if (std::min(a.size(), b.size()) <= BOUNDARY_SCHOOLBOOK_MAX) {
+        std::vector<F> out(len, (F)0);
+        for (size_t i = 0; i < a.size(); i++)
+            for (size_t j = 0; j < b.size(); j++) out[i + j] = HF_CHAIN_ADD(out[i + j], HF_CHAIN_MUL(a[i], b[j]));
+        for (F &v : out) v = HF_CHAIN_END(v);
+        return out;
+    }
+    uint64_t n = 1;
+    while (n < len) n <<= 1;
+    if (n > N) fail(GS_ERR_ARG, "boundary constraints: a product of %zu coefficients needs a root of unity of order %llu", len, (unsigned long long)n);
+    const F w = hf_pow(omega, (hfe)(N / n));
+    std::vector<F> fa(a), fb(b);
+    fa.resize(n, (F)0); fb.resize(n, (F)0);
+    host_transform(fa, w);
+    host_transform(fb, w);
+    for (uint64_t i = 0; i < n; i++) fa[i] = vf_mul(fa[i], fb[i]);
+    host_transform(fa, hf_pow(w, (hfe)(n - 1)));
+    const F ninv = hf_inv((F)n);
+    fa.resize(len);
+    for (F &v : fa) v = vf_mul(v, ninv);
+    return fa;
+}
+std::vector<F> zero_poly_tree(const F *xs, size_t m, F omega, uint64_t N) {
+    if (m <= BOUNDARY_SCHOOLBOOK_MAX) {
+        std::vector<F> zp(m + 1, (F)0);
+        zp[0] = 1;
+        for (size_t i = 0; i < m; i++) {
+            const F nx = hf_sub(0, xs[i]);
+            for (size_t d = i + 1; d >= 1; d--) zp[d] = hf_add(zp[d - 1], hf_mul(zp[d], nx));
+            zp[0] = hf_mul(zp[0], nx);
+        }
+        return zp;
+    }
+    const size_t h = m / 2;
+    return poly_product(zero_poly_tree(xs, h, omega, N), zero_poly_tree(xs + h, m - h, omega, N), omega, N);
+}
+struct BoundaryValues { std::vector<F> i_at, z_at; };
+BoundaryValues boundary_values_direct(const Plan &plan, const Plan::Reg &r, const std::vector<F> &points) {
+    const std::vector<F> ipoly = lagrange(r.xs, r.ys), zpoly = plan.zero_poly(r);
+    BoundaryValues out;
+    for (F x : points) { out.i_at.push_back(horner(ipoly, x)); out.z_at.push_back(horner(zpoly, x)); }
+    return out;
+}
+BoundaryValues boundary_values_tree(const Plan &plan, const Plan::Reg &r, const std::vector<F> &points) {
+    const size_t m = r.steps.size();
+    const uint64_t T = plan.T;
+    if (m > T) fail(GS_ERR_ARG, "Invalid assertion: register %u has %zu assertions, the execution trace %llu steps", r.reg, m, (unsigned long long)T);
+    {
+        std::vector<bool> seen(T, false);
+        for (uint64_t s : r.steps) {
+            if (s >= T) fail(GS_ERR_ARG, "Invalid assertion: step %llu is outside of execution trace", (unsigned long long)s);
+            if (seen[s]) fail(GS_ERR_ARG, "Invalid assertion: step %llu of register %u is asserted more than once", (unsigned long long)s, r.reg);
+            seen[s] = true;
+        }
+    }
+    const std::vector<F> z = zero_poly_tree(r.xs.data(), m, plan.omega, plan.N);
+    std::vector<F> d(T, (F)0);                                       // Z_r' ...
+    for (size_t k = 0; k < m; k++) d[k] = vf_mul((F)(uint64_t)(k + 1), z[k + 1]);
+    host_transform(d, hf_pow(plan.omega, (hfe)plan.E));             // ... at every point of the execution domain
+    std::vector<F> c(m);
+    for (size_t i = 0; i < m; i++) c[i] = d[r.steps[i]];
+    batch_invert(c);
+    for (size_t i = 0; i < m; i++) c[i] = vf_mul(c[i], r.ys[i]);
+    BoundaryValues out;
+    out.z_at = horner_many(z, points);
+    std::vector<F> diff(m);
+    for (size_t q = 0; q < points.size(); q++) {
+        for (size_t i = 0; i < m; i++) diff[i] = hf_sub(points[q], r.xs[i]);
+        batch_invert(diff);
+        F sum = 0;
+        for (size_t i = 0; i < m; i++) sum = HF_CHAIN_ADD(sum, HF_CHAIN_MUL(c[i], diff[i]));
+        out.i_at.push_back(vf_mul(out.z_at[q], HF_CHAIN_END(sum)));
+    }
+    return out;
+}
+
 void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_len) {
     const gs_prover_air &air = job.air;
     const uint64_t E = job.extension_factor;
@@ -370,8 +488,6 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         if (a.step >= T) fail(GS_ERR_ARG, "Invalid assertion: step %llu is outside of execution trace", (unsigned long long)a.step);
     }
     const std::vector<Plan::Reg> &rdata = plan.regs;
-    std::vector<std::vector<F>> ipolys, zpolys;                            // per asserted register: BoundaryConstraints.ts:42, :24-30
-    for (auto &d : rdata) { ipolys.push_back(lagrange(d.xs, d.ys)); zpolys.push_back(plan.zero_poly(d)); }
     const uint32_t bcount = (uint32_t)rdata.size(), dcount = plan.dcount, bcoef = plan.bcoef, V = R + S;
     const std::vector<F> coeffs = plan.coefficients(evRoot, V);
     const F x_last = hf_pow(omega, (hfe)((T - 1) * E));
@@ -477,11 +593,12 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     // (the divisions of all positions share one inversion: first the denominators — x^T - 1 of Z(x), Z_r(x) of every asserted register —
     //  then the values)
     std::vector<F> lcValues, xsq, dens;
-    for (uint64_t step : positions) {
-        const F x = hf_pow(omega, (hfe)step);
-        xsq.push_back(x);
-        dens.push_back(hf_sub(hf_pow(x, (hfe)T), 1));                                                  // ZeroPolynomial.ts:28-34: Z = (x^T - 1) / (x - x_last)
-        for (auto &zp : zpolys) dens.push_back(horner(zp, x));                                      // BoundaryConstraints.ts:55-69
+    for (uint64_t step : positions) xsq.push_back(hf_pow(omega, (hfe)step));
+    std::vector<BoundaryValues> bvals;                                    // per asserted register: I_r and Z_r at every queried point (BoundaryConstraints.ts:42, :24-30)
+    for (auto &d : rdata) bvals.push_back(d.steps.size() <= BOUNDARY_DIRECT_MAX ? boundary_values_direct(plan, d, xsq) : boundary_values_tree(plan, d, xsq));
+    for (size_t pi = 0; pi < positions.size(); pi++) {
+        dens.push_back(hf_sub(hf_pow(xsq[pi], (hfe)T), 1));                                            // ZeroPolynomial.ts:28-34: Z = (x^T - 1) / (x - x_last)
+        for (auto &bv : bvals) dens.push_back(bv.z_at[pi]);                                         // BoundaryConstraints.ts:55-69
     }
     batch_invert(dens);
     for (size_t k = 0; k < static_polys.size(); k++) {                        // K_s(x^(T/period)) at every queried x
@@ -507,7 +624,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         for (size_t k = 0; k < q.size(); k++) qc = hf_add(qc, hf_mul(q[k], coeffs[k]));
         const F dValue = hf_mul(hf_mul(qc, hf_sub(x, x_last)), dens[di++]);                             // Q / Z = Q (x - x_last) / (x^T - 1)
         std::vector<F> b;
-        for (uint32_t r = 0; r < bcount; r++) b.push_back(hf_mul(hf_sub(p[rdata[r].reg], horner(ipolys[r], x)), dens[di++]));
+        for (uint32_t r = 0; r < bcount; r++) b.push_back(hf_mul(hf_sub(p[rdata[r].reg], bvals[r].i_at[pi]), dens[di++]));
         const F xb = hf_pow(x, (hfe)b_inc);
         if (b_inc > 0) for (uint32_t i = 0; i < bcount; i++) b.push_back(hf_mul(b[i], xb));
         F bValue = 0;
@@ -622,6 +739,31 @@ static int verify_entry(const struct gs_prover_job *job, const uint8_t *proof, u
         verify_impl(*job, proof, len);
         return GS_OK;
     });
+}
+// I_r(x) and Z_r(x) of one asserted register at `npoints` points outside the execution domain, for tests (include/gstark_boundary.h)
+static int boundary_at_entry(const uint8_t *omega, uint64_t n, uint64_t steps, const uint64_t *at, const uint8_t *values, uint32_t m, const uint8_t *points,
+                             uint32_t npoints, int method, uint8_t *i_out, uint8_t *z_out, char *err, uint64_t errcap) {
+    if (!omega || !at || !values || !m || (npoints && (!points || !i_out || !z_out)) || (method != 0 && method != 1)) return GS_ERR_ARG;
+    if (!steps || (steps & (steps - 1)) || !n || (n & (n - 1)) || n < steps) return GS_ERR_ARG;
+    return guarded(err, errcap, GS_ERR_OOM, [&]() -> int {
+        Plan plan;
+        plan.T = steps; plan.N = n; plan.E = n / steps; plan.omega = from16(omega);
+        plan.regs.push_back(Plan::Reg{0, {}, {}, {}});
+        Plan::Reg &r = plan.regs[0];
+        for (uint32_t i = 0; i < m; i++) { r.steps.push_back(at[i]); r.ys.push_back(from16(values + ELEM * i)); }
+        plan.fill_xs();
+        std::vector<F> pts(npoints);
+        for (uint32_t q = 0; q < npoints; q++) pts[q] = from16(points + ELEM * q);
+        const BoundaryValues bv = method ? boundary_values_tree(plan, r, pts) : boundary_values_direct(plan, r, pts);
+        for (uint32_t q = 0; q < npoints; q++) { le16(bv.i_at[q], i_out + ELEM * q); le16(bv.z_at[q], z_out + ELEM * q); }
+        return GS_OK;
+    });
+}
+int gs_prover_boundary_at_on(const gs_prover_binding *b, const uint8_t *omega, uint64_t n, uint64_t steps, const uint64_t *at, const uint8_t *values, uint32_t m,
+                             const uint8_t *points, uint32_t npoints, int method, uint8_t *i_out, uint8_t *z_out, char *err, uint64_t errcap) {
+    if (!b) return GS_ERR_ARG;
+    UseApi use(reinterpret_cast<const Api *>(b));
+    return boundary_at_entry(omega, n, steps, at, values, m, points, npoints, method, i_out, z_out, err, errcap);
 }
 int gs_prover_verify(const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap) {
     if (!g_bound) return GS_ERR_UNSUPPORTED;

@@ -436,11 +436,51 @@ class PrimeField:
     def interpolate(self, xs, ys):
         """BoundaryConstraints.ts:42; LowDegreeProver.ts:243 — Lagrange through a handful of points: O(n^2) host
         arithmetic inside the library (gs_small_interpolate), as in the reference's JS layer."""
+        # xs known to be a whole domain {g^i} of a power-of-two order (getPowerSeries of a root of unity) and a library with the device
+        # entry point: the same coefficients without the host path's 4 096-point cap
+        base, n = getattr(xs, 'series_base', None), getattr(xs, 'length', 0)
+        if base is not None and n > 1 and not n & (n - 1) and n == (len(ys) if isinstance(ys, (list, tuple)) else ys.length) \
+                and hasattr(self.backend.lib, 'gs_boundary_polys') and pow(base, n // 2, self.modulus) == self.modulus - 1 \
+                and (self.modulus - 1) % (2 * n) == 0:
+            return self.interpolateAtRoots(base, n, list(range(n)), ys)
         xv = xs if isinstance(xs, (list, tuple)) else xs.toValues()
         yv = ys if isinstance(ys, (list, tuple)) else ys.toValues()
         if len(xv) != len(yv):
             raise GstarkError('Number of x coordinates must be the same as number of y coordinates')
         return self.newVectorFrom(self.interpolateValues(xv, yv))
+
+    def _rootAbove(self, g, order):
+        """a square root of g (g of order `order`, a power of two): an element of order 2 * order, found in the field's 2-power subgroup bit by bit"""
+        p = self.modulus
+        w = self.getRootOfUnity(2 * order)
+        g0, e = w * w % p, 0
+        for i in range(order.bit_length() - 1):
+            if pow(g * pow(pow(g0, e, p), p - 2, p) % p, order >> (i + 1), p) != 1:
+                e |= 1 << i
+        s = pow(w, e, p)
+        if s * s % p != g % p:
+            raise GstarkError(f'interpolateAtRoots: {g} does not generate a domain of {order} points')
+        return s
+
+    def interpolateAtRoots(self, rootOfUnity, order, positions, ys):
+        """The interpolant through (rootOfUnity^positions[i], ys[i]): points of the domain of `order` points (a power of two) that rootOfUnity
+        generates — any generator of it —, distinct positions; built on the device (gs_boundary_polys): any number of points up
+        to `order`, a device vector of len(positions) coefficients, the ones `interpolate` gives for these points.  The field must have a
+        root of unity of order 2 * order (so not its largest power-of-two domain), the library the entry point (the HIP library has it);
+        `interpolate` remains for everything else (host, at most 4 096 points)."""
+        yv = ys if isinstance(ys, (list, tuple)) else ys.toValues()
+        m = len(positions)
+        if m != len(yv):
+            raise GstarkError('Number of x coordinates must be the same as number of y coordinates')
+        if m < 1 or order < 1 or order & (order - 1):
+            raise GstarkError('interpolateAtRoots: at least one point, on a domain of a power-of-two order')
+        if not hasattr(self.backend.lib, 'gs_boundary_polys'):
+            raise GstarkError('this library has no gs_boundary_polys: use interpolate')
+        omega = self._rootAbove(rootOfUnity % self.modulus, order)
+        out, z = Vector(self.backend, m), Vector(self.backend, m + 1)
+        self.backend.call('gs_boundary_polys', self.le(omega), 2 * order, order, (C.c_uint64 * m)(*positions),
+                          b''.join(self.le(y % self.modulus) for y in yv), (C.c_uint32 * 1)(m), 1, m, C.c_void_p(out.ptr), C.c_void_p(z.ptr))
+        return out
 
     def interpolateValues(self, xv, yv):
         n = len(xv)

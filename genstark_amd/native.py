@@ -110,6 +110,11 @@ def _driver(backend):
             lib.gs_prover_sync_phases.restype = None
             lib.gs_prover_member_sequence.argtypes = [C.c_int]
             lib.gs_prover_member_sequence.restype = None
+            lib.gs_prover_host_boundary.argtypes = [C.c_int]
+            lib.gs_prover_host_boundary.restype = None
+            lib.gs_prover_boundary_at_on.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_uint32, C.c_char_p,
+                                                     C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64]
+            lib.gs_prover_boundary_at_on.restype = C.c_int
             lib.gs_prover_prove_dist_on.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Job), C.POINTER(GsComm), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]
             lib.gs_prover_prove_dist_on.restype = C.c_int
             lib.gs_prover_last_collectives.argtypes = [C.POINTER(_Collective), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -433,6 +438,24 @@ class NativeProver:
         """Checking mode of the calling thread's next proofs: the composition tail as the member-by-member sequence of entries instead of
         gs_composition_tail (gs_prover_member_sequence); same bytes."""
         self.lib.gs_prover_member_sequence(1 if on else 0)
+
+    def host_boundary(self, on=True):
+        """Checking mode of the calling thread's next proofs: the boundary polynomials of registers with many assertions on the host
+        (gs_small_interpolate: at most 4096 per register, quadratic) instead of the device (gs_boundary_polys); same bytes."""
+        self.lib.gs_prover_host_boundary(1 if on else 0)
+
+    def boundary_at(self, omega, n, steps, at, values, points, method):
+        """The verifier's I_r(x), Z_r(x) of one register (assertions `values` at steps `at`) at `points` outside the execution domain
+        (gs_prover_boundary_at_on; method 0: the reference's quadratic form, 1: product tree + transform): ([I], [Z])."""
+        f, es = self.field, self.field.elementSize
+        m, q = len(at), len(points)
+        iout, zout, err = C.create_string_buffer(max(q, 1) * es), C.create_string_buffer(max(q, 1) * es), C.create_string_buffer(512)
+        rc = self.lib.gs_prover_boundary_at_on(self.binding, f.le(omega), n, steps, (C.c_uint64 * m)(*at), b''.join(f.le(v % f.modulus) for v in values), m,
+                                               b''.join(f.le(v % f.modulus) for v in points), q, method, C.cast(iout, C.c_void_p), C.cast(zout, C.c_void_p), err, 512)
+        if rc:
+            raise StarkError(err.value.decode(errors='replace') or f'gs_prover_boundary_at failed ({rc})')
+        unpack = lambda raw: [int.from_bytes(raw[i * es:(i + 1) * es], 'little') for i in range(q)]
+        return unpack(iout.raw), unpack(zout.raw)
 
     def sync_phases(self, on=True):
         """Measuring mode for the proofs this THREAD issues next: the device is synchronised at each of the reference's log points, so

@@ -87,6 +87,10 @@ struct gs_prover_job {
     uint32_t extension_factor, exe_query_count, fri_query_count;
     int32_t hash_alg;
     uint8_t root_of_unity[GS_PROVER_ELT_MAX];   /* primitive (steps*extension_factor)-th root: galois getRootOfUnity, computed by the caller */
+    /* Any number of assertions per register up to one per step (distinct steps): with more than 128 on a register the boundary
+     * polynomials are built on the device when the bound library exports gs_boundary_polys (include/gstark_boundary.h), at most 64
+     * asserted registers then; a library without it keeps the host path (at most 4096 per register, quadratic in that count), as does
+     * the distributed driver. */
     const gs_assertion *assertions;
     uint32_t nassertions;
     /* 0: root_of_unity has order steps * extension_factor.  k > 0: it has order 2^k and the driver squares it down to the order of

@@ -418,8 +418,40 @@ class PrimeField {
     addPolys(a, b) { const n = Math.max(a.length, b.length); return this.addVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     subPolys(a, b) { const n = Math.max(a.length, b.length); return this.subVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     mulPolyByConstant(a, c) { return this.mulVectorElements(a, this.mod(c)); }
+    /** a square root of g (g of order `order`, a power of two): an element of order 2 * order, found in the field's 2-power subgroup bit by bit */
+    _rootAbove(g, order) {
+        const w = this.getRootOfUnity(2 * order), g0 = this.mul(w, w);
+        let e = 0n, k = 0;
+        while ((1 << k) < order) k++;
+        for (let i = 0; i < k; i++) {
+            const rest = this.mul(this.mod(g), this.inv(this.exp(g0, e)));
+            if (this.exp(rest, BigInt(order) >> BigInt(i + 1)) !== 1n) e |= 1n << BigInt(i);
+        }
+        const s = this.exp(w, e);
+        if (this.mul(s, s) !== this.mod(g)) throw new Error(`interpolateAtRoots: ${g} does not generate a domain of ${order} points`);
+        return s;
+    }
+    /** The interpolant through (rootOfUnity^positions[i], ys[i]): points of the domain of `order` points (a power of two) that rootOfUnity
+     *  generates, distinct positions — built on the device (gs_boundary_polys; DESIGN 3.7): any number of points up to `order`, a device
+     *  vector of positions.length coefficients, the ones interpolate() gives for these points.  The field must have a root of unity of
+     *  order 2 * order, the library the entry point (the HIP library has it; interpolate() remains for everything else). */
+    interpolateAtRoots(rootOfUnity, order, positions, ys) {
+        this._own(ys);
+        const m = positions.length;
+        if (m !== ys.length) throw new Error('Number of x coordinates must be the same as number of y coordinates');
+        if (m < 1 || order < 1 || (order & (order - 1))) throw new Error('interpolateAtRoots: at least one point, on a domain of a power-of-two order');
+        const omega = this._rootAbove(rootOfUnity, order);
+        const out = new Vector(this, m), z = new Vector(this, m + 1);
+        this.lib.call('gs_boundary_polys', this.ctx, this.le(omega), 2 * order, order, positions, ys.toBuffer(), [m], 1, m, out.ptr, z.ptr);
+        return out;
+    }
     interpolate(xs, ys) {
         this._own(xs, ys);
+        // xs known to be a whole domain {g^i} of a power-of-two order (getPowerSeries of a root of unity) and a library with the device entry
+        // point: the same coefficients without the host path's 4 096-point cap
+        if (xs.seriesBase !== undefined && xs.length > 1 && !(xs.length & (xs.length - 1)) && xs.length === ys.length && this.lib.has && this.lib.has('gs_boundary_polys') &&
+            this.exp(xs.seriesBase, BigInt(xs.length / 2)) === this.modulus - 1n && (this.modulus - 1n) % BigInt(2 * xs.length) === 0n)
+            return this.interpolateAtRoots(xs.seriesBase, xs.length, Array.from({ length: xs.length }, (_, i) => i), ys);
         const n = xs.length, out = Buffer.alloc(this.elementSize * n);
         this.lib.call('gs_small_interpolate', xs.toBuffer(), ys.toBuffer(), n, out);
         const v = new Vector(this, n); this.lib.call('gs_upload', this.ctx, v.ptr, out, out.length); return v;

@@ -113,6 +113,8 @@ const FnDesc kFns[] = {
     {"gs_air_jit_check", "iwiwibiiixiou"},
     {"gs_set_modulus", "bi"},
     {"gs_small_interpolate", "bbio"},
+    // include/gstark_boundary.h: OPTIONAL on a library (symbols are resolved per call: a library without it answers "symbol not found")
+    {"gs_boundary_polys", "cbuuxbwiipp"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
@@ -162,6 +164,27 @@ void throw_foreign(napi_env env, const char *what) {
 
 typedef int (*fn16)(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
+
+// has(name): whether this library exports an entry point of the table — the optional ones (include/gstark_boundary.h) are asked for
+// before they are used
+napi_value Has(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    void *data;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, &data));
+    if (argc < 1) { napi_throw_type_error(env, nullptr, "has(name)"); return nullptr; }
+    Lib *L = lib_of(env, data);
+    if (!L) return nullptr;
+    char name[64];
+    size_t len;
+    if (napi_get_value_string_utf8(env, argv[0], name, sizeof name, &len) != napi_ok) { napi_throw_type_error(env, nullptr, "has(name): the name is a string"); return nullptr; }
+    bool known = false;
+    for (const FnDesc &f : kFns)
+        if (!strcmp(f.name, name)) known = true;
+    napi_value out;
+    NAPI_OK(env, napi_get_boolean(env, known && dlsym(L->dl, name) != nullptr, &out));
+    return out;
+}
 
 // call(name, ...args): generic forwarder.  All ABI parameters are integers or pointers, which the x86-64 SysV
 // calling convention passes in 8-byte slots; narrower parameters read the low bytes of their slot.
@@ -805,6 +828,7 @@ napi_value Open(napi_env env, napi_callback_info info) {
         {"ctxDestroy", nullptr, CtxDestroy, nullptr, nullptr, nullptr, napi_default, L},
         {"alloc", nullptr, Alloc, nullptr, nullptr, nullptr, napi_default, L},
         {"call", nullptr, Call, nullptr, nullptr, nullptr, napi_default, L},
+        {"has", nullptr, Has, nullptr, nullptr, nullptr, napi_default, L},
         {"merkleProveBatch", nullptr, MerkleProveBatch, nullptr, nullptr, nullptr, napi_default, L},
         {"proveMimcSerialized", nullptr, ProveMimcSerialized, nullptr, nullptr, nullptr, napi_default, L},
         {"proveGenericSerialized", nullptr, ProveGenericSerialized, nullptr, nullptr, nullptr, napi_default, L},
@@ -817,7 +841,7 @@ napi_value Open(napi_env env, napi_callback_info info) {
 
 napi_value Init(napi_env env, napi_value exports) {
     const struct { const char *name; napi_callback cb; } fns[] = {
-        {"load", Load}, {"open", Open}, {"fieldInfo", FieldInfo}, {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"alloc", Alloc}, {"call", Call},
+        {"load", Load}, {"open", Open}, {"fieldInfo", FieldInfo}, {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"alloc", Alloc}, {"call", Call}, {"has", Has},
         {"merkleProveBatch", MerkleProveBatch}, {"proveMimcSerialized", ProveMimcSerialized}, {"proveGenericSerialized", ProveGenericSerialized},
         {"packElements", PackElements}, {"unpackElements", UnpackElements},
     };
