@@ -117,8 +117,15 @@ struct Buf {
     uint8_t *at(uint64_t byte_offset) const { return (uint8_t *)p + byte_offset; }
 };
 
-void le16(F v, uint8_t *out) { hf_store(out, v); }          // ELEM bytes, little-endian (the names date from the 128-bit-only driver)
-F from16(const uint8_t *b) { return hf_load(b); }
+// a field element on the ABI and in the proof: ELEM bytes, little-endian
+void store_elem(F v, uint8_t *out) { hf_store(out, v); }
+F load_elem(const uint8_t *b) { return hf_load(b); }
+// ... and as a value, for the scalar arguments of the entry points: enc(v) is built in the argument list and lives until the call returns
+struct Enc {
+    uint8_t b[ELEM];
+    operator const uint8_t *() const { return b; }
+};
+Enc enc(F v) { Enc e; hf_store(e.b, v); return e; }
 
 // ---- galois prng (genstark_amd/field.py: prng — restated) and the index generator -----------------
 F digest_mod_p(const uint8_t d[32]) {          // 256-bit big-endian integer mod p
@@ -384,7 +391,7 @@ Shapes checked_job_shapes(const gs_prover_job &job) {
 }
 // the root of unity of the evaluation domain from the job's (root_of_unity_log2: squared down from a root of higher order)
 F domain_root(const gs_prover_job &job, uint64_t N) {
-    F w = from16(job.root_of_unity);
+    F w = load_elem(job.root_of_unity);
     if (!job.root_of_unity_log2) return w;
     if (job.root_of_unity_log2 > 63 || N > (1ull << job.root_of_unity_log2)) fail(GS_ERR_ARG, "the field has no root of unity of order %llu", (unsigned long long)N);
     for (uint64_t order = 1ull << job.root_of_unity_log2; order > N; order >>= 1) w = hf_mul(w, w);
@@ -544,8 +551,8 @@ static int remainder_check_entry(const uint8_t *values, uint64_t len, uint32_t e
     if (!values || !root_of_unity || !len || (method != 0 && method != 1)) return GS_ERR_ARG;
     return guarded(nullptr, 0, GS_ERR_OOM, [&]() -> int {
         std::vector<F> v(len);
-        for (uint64_t i = 0; i < len; i++) v[i] = from16(values + ELEM * i);
-        return remainder_is_low_degree(v, extension_factor, max_degree_plus1, from16(root_of_unity), method) ? 1 : 0;
+        for (uint64_t i = 0; i < len; i++) v[i] = load_elem(values + ELEM * i);
+        return remainder_is_low_degree(v, extension_factor, max_degree_plus1, load_elem(root_of_unity), method) ? 1 : 0;
     });
 }
 
@@ -573,19 +580,6 @@ int gs_prover_last_stats(struct gs_prover_stats *out) {
 }
 
 }  // extern "C"
-
-namespace {
-
-struct Layer {           // one FRI layer: the tree / rows it queries and the child it produced
-    Tree *pTree;         // tree over the rows of transposeVector(column, 4)
-    const void *column;  // the layer's values in natural order (4 * rows of them); rows are read strided, never transposed
-    uint64_t rows;
-    Tree cTree;          // tree over the next layer's rows
-    Buf next;            // the folded column: `rows` values
-    uint64_t column_length;
-};
-
-}  // namespace
 
 // GSTARK_PROVER_TIMING=1: host wall-clock at the phase boundaries on stderr (no device synchronisation is added, so a phase
 // shows the time until its last BLOCKING call returned)
@@ -686,14 +680,14 @@ static bool remainder_is_low_degree(const std::vector<F> &remainder, uint64_t E,
     F cur = 1;
     for (uint64_t i = 0; i < len; i++) { domain[i] = cur; cur = hf_mul(cur, rou); }
     Bytes xs(m * ELEM), ys(m * ELEM), poly(m * ELEM);
-    for (uint64_t i = 0; i < m; i++) { le16(domain[positions[i]], xs.data() + ELEM * i); le16(remainder[positions[i]], ys.data() + ELEM * i); }
+    for (uint64_t i = 0; i < m; i++) { store_elem(domain[positions[i]], xs.data() + ELEM * i); store_elem(remainder[positions[i]], ys.data() + ELEM * i); }
     if (A.gs_small_interpolate(xs.data(), ys.data(), (uint32_t)m, poly.data())) fail(GS_ERR_ARG, "gs_small_interpolate failed");
     const uint32_t rest = (uint32_t)(positions.size() - m);
     Bytes rx(rest * ELEM), rv(rest * ELEM);
-    for (uint32_t i = 0; i < rest; i++) le16(domain[positions[m + i]], rx.data() + ELEM * i);
+    for (uint32_t i = 0; i < rest; i++) store_elem(domain[positions[m + i]], rx.data() + ELEM * i);
     if (A.gs_small_eval_poly(poly.data(), (uint32_t)m, rx.data(), rest, rv.data())) fail(GS_ERR_ARG, "gs_small_eval_poly failed");
     for (uint32_t i = 0; i < rest; i++)
-        if (from16(rv.data() + ELEM * i) != remainder[positions[m + i]]) return false;
+        if (load_elem(rv.data() + ELEM * i) != remainder[positions[m + i]]) return false;
     return true;
 }
 
@@ -713,19 +707,19 @@ uint64_t composition_factor(const gs_prover_air &air) {
 void interpolate(const std::vector<F> &xs, const std::vector<F> &ys, uint8_t *out) {
     const size_t n = xs.size();
     Bytes xb(n * ELEM), yb(n * ELEM);
-    for (size_t i = 0; i < n; i++) { le16(xs[i], xb.data() + ELEM * i); le16(ys[i], yb.data() + ELEM * i); }
+    for (size_t i = 0; i < n; i++) { store_elem(xs[i], xb.data() + ELEM * i); store_elem(ys[i], yb.data() + ELEM * i); }
     if (A.gs_small_interpolate(xb.data(), yb.data(), (uint32_t)n, out)) fail(GS_ERR_ARG, "gs_small_interpolate failed");
 }
 std::vector<F> lagrange(const std::vector<F> &xs, const std::vector<F> &ys) {
     Bytes cb(xs.size() * ELEM);
     interpolate(xs, ys, cb.data());
     std::vector<F> out(xs.size());
-    for (size_t i = 0; i < out.size(); i++) out[i] = from16(cb.data() + ELEM * i);
+    for (size_t i = 0; i < out.size(); i++) out[i] = load_elem(cb.data() + ELEM * i);
     return out;
 }
 Bytes pack(const std::vector<F> &v, size_t from, size_t count) {
     Bytes b(count * ELEM);
-    for (size_t i = 0; i < count; i++) le16(v[from + i], b.data() + ELEM * i);
+    for (size_t i = 0; i < count; i++) store_elem(v[from + i], b.data() + ELEM * i);
     return b;
 }
 std::vector<uint64_t> augmented_rows(const std::vector<uint64_t> &positions, uint64_t column_length) {      // LowDegreeProver.ts:302-309
@@ -847,7 +841,7 @@ Plan make_plan(const gs_prover_job &job, uint64_t T, uint64_t E, F omega, bool w
         }
         Plan::Reg &r = p.regs[at];
         r.steps.push_back(a.step);
-        r.ys.push_back(from16(a.value));
+        r.ys.push_back(load_elem(a.value));
     }
     if (with_xs) p.fill_xs();
     for (uint32_t i = 0; i < air.nconstraints; i++) {
@@ -876,12 +870,12 @@ void merge_q(Ctx &x, const Plan &plan, const std::vector<F> &co, const std::vect
         Buf pw = powers(plan.combination_degree - g.first);
         if (first) {                                         // every constraint's plain term + this group's adjusted terms
             Bytes adj(nq * ELEM, 0);
-            for (uint32_t i : g.second) le16(co[next++], adj.data() + ELEM * i);
+            for (uint32_t i : g.second) store_elem(co[next++], adj.data() + ELEM * i);
             x.check(A.gs_combine_adjusted(x.c, qa.data(), plain.data(), adj.data(), nq, pw.p, nullptr, n, merged), "gs_combine_adjusted(Q)");
         } else {
             std::vector<const void *> members;
             Bytes adj(g.second.size() * ELEM);
-            for (size_t k = 0; k < g.second.size(); k++) { members.push_back(qa[g.second[k]]); le16(co[next++], adj.data() + ELEM * k); }
+            for (size_t k = 0; k < g.second.size(); k++) { members.push_back(qa[g.second[k]]); store_elem(co[next++], adj.data() + ELEM * k); }
             x.check(A.gs_combine_adjusted(x.c, members.data(), nullptr, adj.data(), (uint32_t)members.size(), pw.p, merged, n, merged), "gs_combine_adjusted(Q)");
         }
         first = false;
@@ -916,8 +910,220 @@ void write_proof(Bytes &out, const Bytes &evRoot, const MerkleProof &evProof, ui
     }
     if (remainder.size() > MAX_ARRAY) fail(GS_ERR_ARG, "remainder too long");
     out.push_back(remainder.size() == MAX_ARRAY ? 0 : (uint8_t)remainder.size());
-    for (F v : remainder) { uint8_t b[ELEM]; le16(v, b); out.insert(out.end(), b, b + ELEM); }
+    for (F v : remainder) { uint8_t b[ELEM]; store_elem(v, b); out.insert(out.end(), b, b + ELEM); }
     write_input_shapes(out, input_shapes);
+}
+
+// ---- the steps both provers issue, each written once --------------------------------------------------------------------------
+// What a job is refused for (the assertions: lib/Stark.ts:356-375).  Each prover runs these where ITS sequence reaches them.
+void check_job(const gs_prover_job &job) {
+    const uint64_t T = job.steps, E = job.extension_factor;
+    if (!T || (T & (T - 1)) || !E || (E & (E - 1)) || !job.air.registers || !job.air.nconstraints || !job.nassertions) fail(GS_ERR_ARG, "invalid job");
+}
+void check_extension_factor(const gs_prover_job &job) {
+    if (job.extension_factor < 2 * composition_factor(job.air)) fail(GS_ERR_ARG, "extension factor must be at least 2x the composition factor");
+}
+void check_fri_length(uint64_t N) {
+    if (N < 128) fail(GS_ERR_ARG, "Invalid array length");
+}
+void check_assertion_ranges(const gs_prover_job &job) {
+    for (uint32_t i = 0; i < job.nassertions; i++) {
+        const gs_assertion &a = job.assertions[i];
+        if (a.reg >= job.air.registers) fail(GS_ERR_ARG, "Invalid assertion: register %u is outside of register bank", a.reg);
+        if (a.step >= job.steps) fail(GS_ERR_ARG, "Invalid assertion: step %llu is outside of execution trace", (unsigned long long)a.step);
+    }
+}
+// cell(i): the bytes the trace holds where assertion i points
+template <class Cell>
+void check_asserted_cells(const gs_prover_job &job, Cell &&cell) {
+    for (uint32_t i = 0; i < job.nassertions; i++)
+        if (memcmp(cell(i), job.assertions[i].value, ELEM))
+            fail(GS_ERR_ARG, "Assertion at step %llu, register %u conflicts with execution trace", (unsigned long long)job.assertions[i].step,
+                 job.assertions[i].reg);
+}
+
+// generateExecutionTrace (lib/Stark.ts:97) into `out`, registers x steps.  first_rows / segments: the job's, or — a rank generating its
+// own segments of a segmented AIR — that rank's
+void launch_trace(Ctx &x, const gs_prover_job &job, const uint8_t *first_rows, uint64_t segments, void *out) {
+    const gs_prover_air &air = job.air;
+    if (air.kind == 0)
+        x.check(A.gs_mimc_trace(x.c, air.seed, air.round_constants, air.nrc, job.steps, out), "gs_mimc_trace");
+    else if (segments)
+        x.check(A.gs_air_trace_segments(x.c, air.t_code, air.t_ninstr, air.i_code, air.i_ninstr, air.consts, air.nconsts, air.vm_regs, air.registers,
+                                        air.static_values, air.static_periods, air.nstatic, first_rows, segments, air.segment_len, out),
+                "gs_air_trace_segments");
+    else
+        x.check(A.gs_air_trace(x.c, air.t_code, air.t_ninstr, air.consts, air.nconsts, air.vm_regs, air.registers, air.static_values, air.static_periods,
+                               air.nstatic, first_rows, job.steps, out), "gs_air_trace");
+}
+
+// The points the composition steps run over: {shift * root^k, k < n}.  The single-device prover works on the whole evaluation domain,
+// {N, omega, 1, E}; rank g of G on its strided share of it, {N / G, omega^G, omega^g, E / G}.  The library takes the whole domain through
+// its plain entry points and a share — rank 0's, whose shift is 1, included — through their _coset twins.
+struct Coset {
+    uint64_t n;
+    F root, shift;
+    uint64_t unit;       // one trace step in powers of root: an assertion at step s is the point root^(s unit); x^T takes `unit` values
+    bool whole;
+};
+// x^e over the points of a coset
+Buf coset_powers(Ctx &x, const Coset &c, uint64_t e) {
+    Buf out(x, c.n * ELEM);
+    x.check(A.gs_power_series(x.c, enc(hf_pow(c.root, (hfe)e)), c.n, out.p), "gs_power_series");
+    if (c.shift != (F)1) x.check(A.gs_vec_mul_scalar(x.c, out.p, enc(hf_pow(c.shift, (hfe)e)), c.n, out.p), "gs_vec_mul_scalar(coset shift)");
+    return out;
+}
+// 1/Z(x) (ZeroPolynomial.ts:36-44 and the division of CompositionPolynomial.ts:117).  x^T - 1 takes only c.unit distinct values: up to 32
+// of them are a table and one product per point inside one kernel; beyond that (no host builds such a statement: extension factors
+// stop at 32) the vectors are formed as the reference forms them
+Buf zero_poly_inverses(Ctx &x, const Plan &plan, const Coset &c) {
+    const uint64_t n = c.n, T = plan.T;
+    const Enc last = enc(hf_pow(plan.omega, (hfe)((T - 1) * plan.E)));                              // :21-23: the last step's point
+    Buf out(x, n * ELEM);
+    if (c.unit <= 32) {
+        if (c.whole) x.check(A.gs_zero_poly_inverses(x.c, enc(c.root), n, T, last, out.p), "gs_zero_poly_inverses");
+        else x.check(A.gs_zero_poly_inverses_coset(x.c, enc(c.root), n, enc(c.shift), T, last, out.p), "gs_zero_poly_inverses_coset");
+        return out;
+    }
+    Buf domain = coset_powers(x, c, 1), xToTheSteps, num(x, n * ELEM), den(x, n * ELEM);
+    if (c.whole) {
+        xToTheSteps = Buf(x, n * ELEM);
+        x.check(A.gs_pluck(x.c, domain.p, n, T, n, xToTheSteps.p), "gs_pluck");                      // :40
+    } else {
+        xToTheSteps = coset_powers(x, c, T);                                                        // pluck(domain, T, N) = (w^T)^i, my share
+    }
+    x.check(A.gs_vec_sub_scalar(x.c, xToTheSteps.p, enc((F)1), n, num.p), "gs_vec_sub_scalar");
+    x.check(A.gs_vec_sub_scalar(x.c, domain.p, last, n, den.p), "gs_vec_sub_scalar");
+    x.check(A.gs_vec_div(x.c, den.p, num.p, n, out.p), "gs_vec_div(1/Z)");
+    return out;
+}
+// 5.4-5.7 and 6 in ONE pass (gs_composition_tail[_coset]) when the assertions fit its per-register limits (tail_fits): D = Q / Z, the
+// boundary quotients from the registers' extensions `pv`, their degree-adjusted merge, and LinearCombination.computeMany (:36-64: the
+// same coefficient stream continues) over the committed vectors on top.  z_inverses null: the kernel makes 1/Z(x) itself
+void composition_tail(Ctx &x, const Plan &plan, const Coset &c, const std::vector<F> &coefficients, const void *qe, const void *z_inverses,
+                      const std::vector<const void *> &pv, const std::vector<const void *> &eVectors, void *out) {
+    const uint32_t bcount = (uint32_t)plan.regs.size(), V = (uint32_t)eVectors.size();
+    const bool adjust = plan.b_inc > 0;
+    const Plan::Boundary bd = plan.boundary(c.unit, true);                // an interpolant through m assertions has m coefficients
+    const Bytes bco = pack(coefficients, plan.dcount, plan.bcoef), cb = pack(coefficients, plan.dcount + plan.bcoef, plan.lccount(V));
+    const Enc last = enc(hf_pow(plan.omega, (hfe)((plan.T - 1) * plan.E)));                         // ZeroPolynomial.ts:21-23
+    if (c.whole)
+        x.check(A.gs_composition_tail(x.c, c.n, enc(c.root), qe, z_inverses, plan.T, last, pv.data(), bcount, bd.interpolants.data(), bd.width, bd.at.data(),
+                                      bd.per_row.data(), bd.width, bco.data(), adjust ? bco.data() + ELEM * bcount : nullptr, eVectors.data(), V, cb.data(),
+                                      adjust ? cb.data() + ELEM * V : nullptr, nullptr, plan.b_inc, nullptr, out), "gs_composition_tail");
+    else
+        x.check(A.gs_composition_tail_coset(x.c, c.n, enc(c.root), enc(c.shift), qe, z_inverses, plan.T, last, pv.data(), bcount, bd.interpolants.data(), bd.width,
+                                            bd.at.data(), bd.per_row.data(), bd.width, bco.data(), adjust ? bco.data() + ELEM * bcount : nullptr, eVectors.data(), V,
+                                            cb.data(), adjust ? cb.data() + ELEM * V : nullptr, nullptr, plan.b_inc, nullptr, out), "gs_composition_tail_coset");
+}
+// ... and the same member by member -> cEval; qe and zInverses are consumed.
+// device_boundary: I_r and Z_r are built on the device (gs_boundary_polys: the whole domain only) instead of this host core
+void member_sequence(Ctx &x, const Plan &plan, const Coset &c, bool device_boundary, const std::vector<F> &coefficients, Buf &qe, Buf &zInverses,
+                     const std::vector<const void *> &pv, const Buf &psbPowers, void *cEval) {
+    const uint64_t n = c.n;
+    const uint32_t bcount = (uint32_t)plan.regs.size();
+    // 5.4 D(x) = Q(x) / Z(x) (:113-121)
+    Buf dEval(x, n * ELEM);
+    x.check(A.gs_vec_mul(x.c, qe.p, zInverses.p, n, dEval.p), "gs_vec_mul(D)");
+    qe.release();
+    zInverses.release();
+    // 5.5 boundary constraints (BoundaryConstraints.ts:71-95)
+    const Plan::Boundary bd = plan.boundary(c.unit, false);
+    const uint32_t ilen = bd.width, zlen = bd.width + 1;                  // m assertions: m interpolant coefficients, m + 1 of Z_r
+    if (!c.whole && (ilen > n || zlen > n)) fail(GS_ERR_UNSUPPORTED, "more assertions on a register than points per rank");
+    // rows of coefficients for the device; on a share a polynomial is evaluated at shift * root^k: its coefficients scaled by shift^j
+    auto upload_rows = [&](const std::vector<std::vector<F>> &rows, size_t len) {
+        Bytes host(rows.size() * len * ELEM, 0);                        // shorter rows are zero-extended (newMatrixFromVectors)
+        for (size_t r = 0; r < rows.size(); r++) {
+            F sj = 1;
+            for (size_t k = 0; k < rows[r].size(); k++) {
+                store_elem(c.whole ? rows[r][k] : hf_mul(rows[r][k], sj), host.data() + (r * len + k) * ELEM);
+                if (!c.whole) sj = hf_mul(sj, c.shift);
+            }
+        }
+        Buf b(x, host.size());
+        x.check(A.gs_upload(x.c, b.p, host.data(), host.size()), "gs_upload(boundary polynomials)");
+        return b;
+    };
+    Buf iPolys, zPolys;
+    if (device_boundary) {
+        iPolys = Buf(x, (uint64_t)bcount * ilen * ELEM);
+        zPolys = Buf(x, (uint64_t)bcount * zlen * ELEM);
+        std::vector<uint64_t> at((size_t)bcount * bd.width, 0);
+        Bytes ys((size_t)bcount * bd.width * ELEM, 0);
+        for (uint32_t r = 0; r < bcount; r++)
+            for (size_t k = 0; k < plan.regs[r].steps.size(); k++) {
+                at[(size_t)r * bd.width + k] = plan.regs[r].steps[k];
+                store_elem(plan.regs[r].ys[k], ys.data() + ((size_t)r * bd.width + k) * ELEM);
+            }
+        x.check(A.gs_boundary_polys(x.c, enc(plan.omega), plan.N, plan.T, at.data(), ys.data(), bd.per_row.data(), bcount, bd.width, iPolys.p, zPolys.p),
+                "gs_boundary_polys");
+    } else {
+        std::vector<std::vector<F>> ipolys;
+        for (auto &r : plan.regs) ipolys.push_back(lagrange(r.xs, r.ys));
+        iPolys = upload_rows(ipolys, ilen);
+    }
+    Buf iValues(x, (uint64_t)bcount * n * ELEM), pi(x, (uint64_t)bcount * n * ELEM), bEval(x, (uint64_t)bcount * n * ELEM);
+    x.check(counted_eval_polys_at_roots(x.c, iPolys.p, bcount, ilen, enc(c.root), n, iValues.p), "gs_eval_polys_at_roots(I)");
+    x.check(A.gs_sub_matrix_from_vectors(x.c, pv.data(), iValues.p, bcount, n, pi.p), "gs_sub_matrix_from_vectors");
+    if (bd.width <= 4) {
+        // the divisors' roots are points root^j of the domain: look-ups in its table 1 / (shift root^j - 1) instead of evaluating Z_r(x)
+        // and inverting it (same values: BoundaryConstraints.ts:88,92)
+        if (c.whole) x.check(A.gs_div_by_domain_roots(x.c, pi.p, bcount, n, enc(c.root), bd.at.data(), bd.per_row.data(), bd.width, bEval.p), "gs_div_by_domain_roots");
+        else x.check(A.gs_div_by_domain_roots_coset(x.c, pi.p, bcount, n, enc(c.root), enc(c.shift), bd.at.data(), bd.per_row.data(), bd.width, bEval.p),
+                     "gs_div_by_domain_roots_coset");
+    } else {
+        if (!device_boundary) {
+            std::vector<std::vector<F>> zpolys;
+            for (auto &r : plan.regs) zpolys.push_back(plan.zero_poly(r));
+            zPolys = upload_rows(zpolys, zlen);
+        }
+        Buf zValues(x, (uint64_t)bcount * n * ELEM);
+        x.check(counted_eval_polys_at_roots(x.c, zPolys.p, bcount, zlen, enc(c.root), n, zValues.p), "gs_eval_polys_at_roots(Zb)");
+        x.check(A.gs_vec_div(x.c, pi.p, zValues.p, (uint64_t)bcount * n, bEval.p), "gs_vec_div(B)");
+    }
+    iValues.release(); pi.release();
+    // 5.6 degree adjustment of B (:124-138) and 5.7 merge (:140-146), with D added in the same pass
+    const Bytes bco = pack(coefficients, plan.dcount, plan.bcoef);
+    std::vector<const void *> ba;
+    for (uint32_t i = 0; i < bcount; i++) ba.push_back(bEval.at((uint64_t)i * n * ELEM));
+    x.check(A.gs_combine_adjusted(x.c, ba.data(), bco.data(), plan.b_inc > 0 ? bco.data() + ELEM * bcount : nullptr, bcount, plan.b_inc > 0 ? psbPowers.p : nullptr,
+                                  dEval.p, n, cEval), "gs_combine_adjusted(B + D)");
+}
+// 6 random linear combination (LinearCombination.ts:36-64).  psIncrementalDegree = compositionDegree - T: the same powers as B's;
+// P_r o powers is not materialised, C is added in the pass
+void linear_combination(Ctx &x, const Plan &plan, const std::vector<F> &coefficients, const std::vector<const void *> &eVectors, const Buf &psbPowers,
+                        const void *cEval, uint64_t n, void *lEval) {
+    const uint32_t V = (uint32_t)eVectors.size();
+    const Bytes cb = pack(coefficients, plan.dcount + plan.bcoef, plan.lccount(V));
+    x.check(A.gs_combine_adjusted(x.c, eVectors.data(), cb.data(), plan.b_inc > 0 ? cb.data() + ELEM * V : nullptr, V, plan.b_inc > 0 ? psbPowers.p : nullptr, cEval, n,
+                                  lEval), "gs_combine_adjusted(L)");
+}
+
+// One FRI layer's products: the folded column (a quarter of the layer's values) and the tree over its rows
+struct Fold { Buf next; Tree cTree; };
+// LowDegreeProver.ts:176-221 on a column that is whole and in natural order, the recursion unrolled: every layer's buffers first, then
+// ONE call (gs_fri_layers = per layer gs_fri_fold_at :189-198 + gs_merkle_commit_rows_seed :201-202, with as few dependent launches as
+// the sizes allow).  `column`: len values, layer log4(step) of a domain of N points; `point`: where its first fold is taken, on the device
+std::vector<Fold> fri_layers(Ctx &x, int alg, F omega, uint64_t N, uint64_t step, const void *column, uint64_t len, const void *point) {
+    std::vector<Fold> folds;
+    for (uint64_t l = len; l > 256; l /= 4) {
+        const uint64_t rows = l / 4;
+        folds.emplace_back();
+        Fold &f = folds.back();
+        f.next = Buf(x, rows * ELEM);
+        f.cTree.n = rows / 4;
+        f.cTree.leaves = Buf(x, rows / 4 * DIGEST);
+        f.cTree.nodes = Buf(x, rows / 4 * DIGEST);
+        if (rows > 256) f.cTree.point = Buf(x, ELEM);                                                 // (no layer below the last tree)
+        f.cTree.root.resize(DIGEST);
+    }
+    if (folds.empty()) return folds;
+    std::vector<gs_fri_layer> outs(folds.size());
+    for (size_t d = 0; d < folds.size(); d++) outs[d] = gs_fri_layer{folds[d].next.p, folds[d].cTree.leaves.p, folds[d].cTree.nodes.p, folds[d].cTree.point.p, 0};
+    x.check(A.gs_fri_layers(x.c, (gs_hash_alg)alg, enc(omega), N, step, column, len, point, (uint32_t)outs.size(), outs.data()), "gs_fri_layers");
+    for (size_t d = 0; d < folds.size(); d++) folds[d].cTree.ticket = outs[d].ticket;
+    return folds;
 }
 
 }  // namespace
@@ -928,14 +1134,14 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     const uint64_t T = job.steps, E = job.extension_factor, N = T * E;
     const uint32_t R = air.registers;
     const int alg = job.hash_alg;
-    if (!T || (T & (T - 1)) || !E || (E & (E - 1)) || !R || !air.nconstraints || !job.nassertions) fail(GS_ERR_ARG, "invalid job");
+    check_job(job);
     const Shapes input_shapes = checked_job_shapes(job);          // iShapes of the proof (lib/Stark.ts:161); empty without input registers
-    if (E < 2 * composition_factor(air)) fail(GS_ERR_ARG, "extension factor must be at least 2x the composition factor");
+    check_extension_factor(job);
     const F omega = domain_root(job, N);
     Plan plan = make_plan(job, T, E, omega, false);
     const uint64_t Nc = plan.Nc, combination_degree = plan.combination_degree, b_inc = plan.b_inc;
     const F comp_rou = hf_pow(omega, (hfe)(N / Nc)), exec_rou = hf_pow(omega, (hfe)E);
-    uint8_t s16[ELEM], s16b[ELEM];
+    const Coset domain{N, omega, 1, E, true};                     // the whole evaluation domain
 
     // 1 ----- evaluation context (lib/Stark.ts:92-94): the kernels below derive domain points from omega; the evaluation domain is
     // materialised only by the general Z(x) sequence
@@ -950,7 +1156,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     // the generic sequence's tail in one pass (gs_composition_tail) when the assertions fit its per-register limits: neither 1/Z(x) nor
     // the power series of the degree adjustment is materialised then
     const bool tail = !fused && tail_fits(job, R + air.nsecret);
-    const bool tail_makes_z = tail && E <= 32;
+    const bool tail_makes_z = tail && domain.unit <= 32;
     // registers with many assertions: I_r and Z_r are built on the device (gs_boundary_polys) where the bound
     // library has that entry point — otherwise, and for the few assertions of every other statement, on this host core
     uint32_t most_assertions = 0;
@@ -962,31 +1168,10 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
                                  most_assertions <= T && T <= (1ull << 28);
     if (!device_boundary) plan.fill_xs();
     Buf zInverses;
-    if (!fused && !tail_makes_z) {
-        zInverses = Buf(x, N * ELEM);
-        // ZeroPolynomial.ts:36-44 and the division of CompositionPolynomial.ts:117 in one kernel: x^T - 1 takes only E distinct values
-        le16(omega, s16);
-        le16(hf_pow(omega, (hfe)((T - 1) * E)), s16b);                                               // :21-23
-        if (E <= 32) {
-            x.check(A.gs_zero_poly_inverses(x.c, s16, N, T, s16b, zInverses.p), "gs_zero_poly_inverses");
-        } else {
-            Buf evalDomain(x, N * ELEM), xToTheSteps(x, N * ELEM), num(x, N * ELEM), den(x, N * ELEM);
-            le16(omega, s16);
-            x.check(A.gs_power_series(x.c, s16, N, evalDomain.p), "gs_power_series(evaluation domain)");
-            x.check(A.gs_pluck(x.c, evalDomain.p, N, T, N, xToTheSteps.p), "gs_pluck");                // ZeroPolynomial.ts:40
-            le16(1, s16);
-            x.check(A.gs_vec_sub_scalar(x.c, xToTheSteps.p, s16, N, num.p), "gs_vec_sub_scalar");
-            x.check(A.gs_vec_sub_scalar(x.c, evalDomain.p, s16b, N, den.p), "gs_vec_sub_scalar");
-            x.check(A.gs_vec_div(x.c, den.p, num.p, N, zInverses.p), "gs_vec_div(1/Z)");               // CompositionPolynomial.ts:117
-        }
-    }
+    if (!fused && !tail_makes_z) zInverses = zero_poly_inverses(x, plan, domain);
     Buf psbPowers;                                                 // x^(compositionDegree - T) over the evaluation domain
     const bool lc_folds = fused && R + air.nsecret == 1;           // LinearCombination folded into the composition kernel too
-    if (b_inc > 0 && !lc_folds && !tail) {                         // also what LinearCombination.ts:44-52 multiplies by
-        psbPowers = Buf(x, N * ELEM);
-        le16(hf_pow(omega, (hfe)b_inc), s16);
-        x.check(A.gs_power_series(x.c, s16, N, psbPowers.p), "gs_power_series(psb)");
-    }
+    if (b_inc > 0 && !lc_folds && !tail) psbPowers = coset_powers(x, domain, b_inc);       // also what LinearCombination.ts:44-52 multiplies by
 
     // MiMC: the cyclic register K over the evaluation domain — its 64 coefficients from the composition-domain table, then its values
     // at the (k_len * N/Nc)-th roots of unity (the constraint is evaluated on all N points from the extension of P)
@@ -996,43 +1181,27 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         klen_n = air.k_len * (N / Nc);
         Buf kPoly(x, air.k_len * ELEM);
         kN = Buf(x, klen_n * ELEM);
-        le16(hf_pow(omega, (hfe)(N / air.k_len)), s16);
-        x.check(counted_interpolate_roots(x.c, air.k_table, 1, s16, air.k_len, kPoly.p), "gs_interpolate_roots(K)");
-        le16(hf_pow(omega, (hfe)(N / klen_n)), s16);
-        x.check(counted_eval_polys_at_roots(x.c, kPoly.p, 1, air.k_len, s16, klen_n, kN.p), "gs_eval_polys_at_roots(K)");
+        x.check(counted_interpolate_roots(x.c, air.k_table, 1, enc(hf_pow(omega, (hfe)(N / air.k_len))), air.k_len, kPoly.p), "gs_interpolate_roots(K)");
+        x.check(counted_eval_polys_at_roots(x.c, kPoly.p, 1, air.k_len, enc(hf_pow(omega, (hfe)(N / klen_n))), klen_n, kN.p), "gs_eval_polys_at_roots(K)");
     }
 
     clock.mark("context + trace-independent work issued");
     clock.readme(x, "Set up evaluation context");
     // 2 ----- execution trace (:97) and the assertions it must satisfy (:356-375)
     Buf trace(x, (uint64_t)R * T * ELEM);
-    if (air.kind == 0)
-        x.check(A.gs_mimc_trace(x.c, air.seed, air.round_constants, air.nrc, T, trace.p), "gs_mimc_trace");
-    else if (air.segments)
-        x.check(A.gs_air_trace_segments(x.c, air.t_code, air.t_ninstr, air.i_code, air.i_ninstr, air.consts, air.nconsts, air.vm_regs, R,
-                                        air.static_values, air.static_periods, air.nstatic, air.first_rows, air.segments, air.segment_len, trace.p),
-                "gs_air_trace_segments");
-    else
-        x.check(A.gs_air_trace(x.c, air.t_code, air.t_ninstr, air.consts, air.nconsts, air.vm_regs, R, air.static_values, air.static_periods,
-                               air.nstatic, air.first_rows, T, trace.p), "gs_air_trace");
+    launch_trace(x, job, air.first_rows, air.segments, trace.p);
     // the asserted cells (:356-375) are compared when the evaluation root comes back: one round trip for both
+    check_assertion_ranges(job);
     std::vector<uint64_t> asserted_at;
-    for (uint32_t i = 0; i < job.nassertions; i++) {
-        const gs_assertion &a = job.assertions[i];
-        if (a.reg >= R) fail(GS_ERR_ARG, "Invalid assertion: register %u is outside of register bank", a.reg);
-        if (a.step >= T) fail(GS_ERR_ARG, "Invalid assertion: step %llu is outside of execution trace", (unsigned long long)a.step);
-        asserted_at.push_back((uint64_t)a.reg * T + a.step);
-    }
+    for (uint32_t i = 0; i < job.nassertions; i++) asserted_at.push_back((uint64_t)job.assertions[i].reg * T + job.assertions[i].step);
 
     clock.mark("execution trace (host recurrence)");
     clock.readme(x, "Generated execution trace");
     // 3 ----- P(x) and its low-degree extension (:106-109)
     Buf pPolys(x, (uint64_t)R * T * ELEM), pEval(x, (uint64_t)R * N * ELEM);
-    le16(exec_rou, s16);
-    x.check(counted_interpolate_roots(x.c, trace.p, R, s16, T, pPolys.p), "gs_interpolate_roots(trace)");
+    x.check(counted_interpolate_roots(x.c, trace.p, R, enc(exec_rou), T, pPolys.p), "gs_interpolate_roots(trace)");
     clock.readme(x, "Computed execution trace polynomials P(x)");
-    le16(omega, s16);
-    x.check(counted_eval_polys_at_roots(x.c, pPolys.p, R, T, s16, N, pEval.p), "gs_eval_polys_at_roots(P)");
+    x.check(counted_eval_polys_at_roots(x.c, pPolys.p, R, T, enc(omega), N, pEval.p), "gs_eval_polys_at_roots(P)");
     clock.readme(x, "Low-degree extended P(x) polynomials over evaluation domain");
     std::vector<const void *> pRows(R);
     for (uint32_t r = 0; r < R; r++) pRows[r] = pEval.at((uint64_t)r * N * ELEM);
@@ -1046,7 +1215,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     clock.mark("P(x), extension, evaluation tree issued");
     clock.readme(x, "Serialized evaluations of P(x) and S(x) polynomials + Built evaluation merkle tree (one fused call)");
     // 5 ----- composition polynomial (CompositionPolynomial.ts:29-146)
-    const uint32_t bcount = (uint32_t)plan.regs.size(), dcount = plan.dcount, bcoef = plan.bcoef;
+    const uint32_t dcount = plan.dcount, bcoef = plan.bcoef;
     // The coefficients come from the evaluation root (:121): it is read where the first of them is needed, with the asserted cells —
     // the work that needs neither (constraint evaluation, degree adjustment) is queued first and covers the round trip
     std::vector<F> coefficients;
@@ -1057,10 +1226,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         x.check(A.gs_gather(x.c, trace.p, ELEM, asserted_at.data(), asserted_at.size(), got.data()), "gs_gather(asserted cells)");
         x.check(A.gs_gather(x.c, eTree.nodes.p, DIGEST, &one, 1, eTree.root.data()), "gs_gather(root)");
         win.end();
-        for (uint32_t i = 0; i < job.nassertions; i++)
-            if (memcmp(got.data() + i * ELEM, job.assertions[i].value, ELEM))
-                fail(GS_ERR_ARG, "Assertion at step %llu, register %u conflicts with execution trace", (unsigned long long)job.assertions[i].step,
-                     job.assertions[i].reg);
+        check_asserted_cells(job, [&](uint32_t i) { return got.data() + i * ELEM; });
         trace.release();
         coefficients = plan.coefficients(eTree.root, V);
     };
@@ -1074,24 +1240,23 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         read_evaluation_root();
         const bool q_adjusted = plan.groups[0].first < combination_degree;
         Bytes co(4 * ELEM, 0);
-        le16(coefficients[0], co.data());
-        if (q_adjusted) le16(coefficients[1], co.data() + ELEM);
-        le16(coefficients[dcount], co.data() + 2 * ELEM);
-        if (b_inc > 0) le16(coefficients[dcount + 1], co.data() + 3 * ELEM);
+        store_elem(coefficients[0], co.data());
+        if (q_adjusted) store_elem(coefficients[1], co.data() + ELEM);
+        store_elem(coefficients[dcount], co.data() + 2 * ELEM);
+        if (b_inc > 0) store_elem(coefficients[dcount + 1], co.data() + 3 * ELEM);
         // ... and, with one committed vector, LinearCombination.computeMany (:36-64) on top: the same prng stream continues
         lc_fused = lc_folds;
         Bytes lc = lc_folds ? pack(coefficients, dcount + bcoef, plan.lccount(V)) : Bytes();
         lc.resize(2 * ELEM, 0);                                    // (the kernel reads two; the second is 0 without a degree adjustment)
-        le16(omega, s16);
-        x.check(A.gs_mimc_composition(x.c, pRows[0], N, T, s16, kN.p, klen_n, co.data(), q_adjusted ? combination_degree - plan.groups[0].first : 0, b_inc,
+        x.check(A.gs_mimc_composition(x.c, pRows[0], N, T, enc(omega), kN.p, klen_n, co.data(), q_adjusted ? combination_degree - plan.groups[0].first : 0, b_inc,
                                       bd.interpolants.data(), bd.at.data(), bd.per_row[0], lc_folds ? lc.data() : nullptr, cEval.p), "gs_mimc_composition");
     } else {
         // 5.1-5.3: the combined, degree-adjusted Q has degree < Nc, so its extension to the evaluation domain (:109-110) is what
         // the constraint expression gives there.  MiMC (one cheap constraint): evaluate it on all N points from the extension of P
         // already at hand — no interpolation + extension; AIR programs: on the composition domain as the reference does.
         const bool direct = air.kind == 0;
-        const uint64_t Nq = direct ? N : Nc;
-        const F q_rou = direct ? omega : comp_rou;
+        const Coset qDomain = direct ? domain : Coset{Nc, comp_rou, 1, Nc / T, true};
+        const uint64_t Nq = qDomain.n;
         Buf q(x, (uint64_t)air.nconstraints * Nq * ELEM);
         if (direct) {
             x.check(A.gs_mimc_constraints(x.c, pRows[0], N, N / T, kN.p, klen_n, q.p), "gs_mimc_constraints");
@@ -1108,90 +1273,23 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         read_evaluation_root();
         Buf qe(x, N * ELEM), qc;
         if (!direct) qc = Buf(x, Nc * ELEM);
-        merge_q(x, plan, coefficients, qa, Nq, [&](uint64_t e) {
-            Buf powers(x, Nq * ELEM);
-            le16(hf_pow(q_rou, (hfe)e), s16);
-            x.check(A.gs_power_series(x.c, s16, Nq, powers.p), "gs_power_series(q powers)");
-            return powers;
-        }, direct ? qe.p : qc.p);
+        merge_q(x, plan, coefficients, qa, Nq, [&](uint64_t e) { return coset_powers(x, qDomain, e); }, direct ? qe.p : qc.p);
         if (!direct) {
             Buf qcPoly(x, Nc * ELEM);
-            le16(comp_rou, s16);
-            x.check(counted_interpolate_roots(x.c, qc.p, 1, s16, Nc, qcPoly.p), "gs_interpolate_roots(Q)");
-            le16(omega, s16);
-            x.check(counted_eval_polys_at_roots(x.c, qcPoly.p, 1, Nc, s16, N, qe.p), "gs_eval_polys_at_roots(Q)");
+            x.check(counted_interpolate_roots(x.c, qc.p, 1, enc(comp_rou), Nc, qcPoly.p), "gs_interpolate_roots(Q)");
+            x.check(counted_eval_polys_at_roots(x.c, qcPoly.p, 1, Nc, enc(omega), N, qe.p), "gs_eval_polys_at_roots(Q)");
         }
-        // 5.4-5.7 and 6 in ONE pass (gs_composition_tail): D = Q / Z, the boundary quotients from the registers' extensions, their
-        // degree-adjusted merge, and LinearCombination.computeMany on top — when the assertions fit its per-register limits
+        // 5.4-5.7: in ONE pass with 6 on top (gs_composition_tail) when the assertions fit its per-register limits, else member by member
         std::vector<const void *> pv;                                      // the asserted registers' extensions
         for (auto &r : plan.regs) pv.push_back(pRows[r.reg]);
-        const Bytes bco = pack(coefficients, dcount, bcoef);
         if (tail) {
-            const Plan::Boundary bd = plan.boundary(E, true);              // an interpolant through m assertions has m coefficients
-            const Bytes cb = pack(coefficients, dcount + bcoef, plan.lccount(V));      // LinearCombination.ts:36-64: the same stream continues
-            le16(omega, s16);
-            le16(hf_pow(omega, (hfe)((T - 1) * E)), s16b);                                           // ZeroPolynomial.ts:21-23: the last step's point
-            x.check(A.gs_composition_tail(x.c, N, s16, qe.p, tail_makes_z ? nullptr : zInverses.p, T, s16b, pv.data(), bcount, bd.interpolants.data(), bd.width,
-                                          bd.at.data(), bd.per_row.data(), bd.width, bco.data(), b_inc > 0 ? bco.data() + ELEM * bcount : nullptr, eVectors.data(), V,
-                                          cb.data(), b_inc > 0 ? cb.data() + ELEM * V : nullptr, nullptr, b_inc, nullptr, cEval.p), "gs_composition_tail");
+            composition_tail(x, plan, domain, coefficients, qe.p, tail_makes_z ? nullptr : zInverses.p, pv, eVectors, cEval.p);
             lc_fused = true;
         } else {
-        // 5.4 D(x) = Q(x) / Z(x) (:113-121)
-        Buf dEval(x, N * ELEM);
-        x.check(A.gs_vec_mul(x.c, qe.p, zInverses.p, N, dEval.p), "gs_vec_mul(D)");
-        // 5.5 boundary constraints (BoundaryConstraints.ts:71-95)
-        std::vector<std::vector<F>> ipolys, zpolys;
-        if (!device_boundary)
-            for (auto &r : plan.regs) { ipolys.push_back(lagrange(r.xs, r.ys)); zpolys.push_back(plan.zero_poly(r)); }
-        auto upload_rows = [&](const std::vector<std::vector<F>> &rows, size_t len) {
-            Bytes host(rows.size() * len * ELEM, 0);                    // shorter rows are zero-extended (newMatrixFromVectors)
-            for (size_t r = 0; r < rows.size(); r++)
-                for (size_t k = 0; k < rows[r].size(); k++) le16(rows[r][k], host.data() + (r * len + k) * ELEM);
-            Buf b(x, host.size());
-            x.check(A.gs_upload(x.c, b.p, host.data(), host.size()), "gs_upload(boundary polynomials)");
-            return b;
-        };
-        const Plan::Boundary bd = plan.boundary(E, false);
-        const uint32_t ilen = bd.width, zlen = bd.width + 1;              // m assertions: m interpolant coefficients, m + 1 of Z_r
-        Buf iPolys, zPolys;
-        if (device_boundary) {
-            iPolys = Buf(x, (uint64_t)bcount * ilen * ELEM);
-            zPolys = Buf(x, (uint64_t)bcount * zlen * ELEM);
-            std::vector<uint64_t> at((size_t)bcount * bd.width, 0);
-            Bytes ys((size_t)bcount * bd.width * ELEM, 0);
-            for (uint32_t r = 0; r < bcount; r++)
-                for (size_t k = 0; k < plan.regs[r].steps.size(); k++) {
-                    at[(size_t)r * bd.width + k] = plan.regs[r].steps[k];
-                    le16(plan.regs[r].ys[k], ys.data() + ((size_t)r * bd.width + k) * ELEM);
-                }
-            le16(omega, s16);
-            x.check(A.gs_boundary_polys(x.c, s16, N, T, at.data(), ys.data(), bd.per_row.data(), bcount, bd.width, iPolys.p, zPolys.p), "gs_boundary_polys");
-        } else {
-            iPolys = upload_rows(ipolys, ilen);
-        }
-        Buf iValues(x, (uint64_t)bcount * N * ELEM), pi(x, (uint64_t)bcount * N * ELEM), bEval(x, (uint64_t)bcount * N * ELEM);
-        le16(omega, s16);
-        x.check(counted_eval_polys_at_roots(x.c, iPolys.p, bcount, ilen, s16, N, iValues.p), "gs_eval_polys_at_roots(I)");
-        x.check(A.gs_sub_matrix_from_vectors(x.c, pv.data(), iValues.p, bcount, N, pi.p), "gs_sub_matrix_from_vectors");
-        if (bd.width <= 4) {
-            // the divisors' roots are domain points: look-ups in the domain's table 1/(omega^j - 1) instead of evaluating Z_r(x)
-            // and inverting it (same values: BoundaryConstraints.ts:88,92)
-            x.check(A.gs_div_by_domain_roots(x.c, pi.p, bcount, N, s16, bd.at.data(), bd.per_row.data(), bd.width, bEval.p), "gs_div_by_domain_roots");
-        } else {
-            if (!device_boundary) zPolys = upload_rows(zpolys, zlen);
-            Buf zValues(x, (uint64_t)bcount * N * ELEM);
-            x.check(counted_eval_polys_at_roots(x.c, zPolys.p, bcount, zlen, s16, N, zValues.p), "gs_eval_polys_at_roots(Zb)");
-            x.check(A.gs_vec_div(x.c, pi.p, zValues.p, (uint64_t)bcount * N, bEval.p), "gs_vec_div(B)");
-        }
-        iValues.release(); pi.release();
-        // 5.6 degree adjustment of B (:124-138) and 5.7 merge (:140-146), with D added in the same pass
-        std::vector<const void *> ba;
-        for (uint32_t i = 0; i < bcount; i++) ba.push_back(bEval.at((uint64_t)i * N * ELEM));
-        x.check(A.gs_combine_adjusted(x.c, ba.data(), bco.data(), b_inc > 0 ? bco.data() + ELEM * bcount : nullptr, bcount, b_inc > 0 ? psbPowers.p : nullptr,
-                                      dEval.p, N, cEval.p), "gs_combine_adjusted(B + D)");
+            member_sequence(x, plan, domain, device_boundary, coefficients, qe, zInverses, pv, psbPowers, cEval.p);
         }
     }
-    if (!fused) zInverses.release();
+    zInverses.release();
 
     clock.readme(x, lc_fused ? "Computed composition polynomial C(x) + Combined P(x) and S(x) evaluations with C(x) evaluations (one kernel)"
                             : "Computed composition polynomial C(x)");
@@ -1201,10 +1299,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         lEval = std::move(cEval);
     } else {
         lEval = Buf(x, N * ELEM);
-        // psIncrementalDegree = compositionDegree - T: the same powers as B's; P_r o powers is not materialised, C is added in the pass
-        const Bytes cb = pack(coefficients, dcount + bcoef, plan.lccount(V));
-        x.check(A.gs_combine_adjusted(x.c, eVectors.data(), cb.data(), b_inc > 0 ? cb.data() + ELEM * V : nullptr, V, b_inc > 0 ? psbPowers.p : nullptr, cEval.p, N,
-                                      lEval.p), "gs_combine_adjusted(L)");
+        linear_combination(x, plan, coefficients, eVectors, psbPowers, cEval.p, N, lEval.p);
     }
     cEval.release();
     psbPowers.release();
@@ -1212,59 +1307,23 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     if (!lc_fused) clock.readme(x, "Combined P(x) and S(x) evaluations with C(x) evaluations");
     clock.mark("composition + LC issued (root read inside)");
     // 7 ----- low-degree proof (LowDegreeProver.ts:39-68, 176-221)
-    if (N < 128) fail(GS_ERR_ARG, "Invalid array length");
+    check_fri_length(N);
     // transposeVector(v, 4) is never materialised: row r of it is v[r], v[r + rows], v[r + 2 rows], v[r + 3 rows], which the hashing,
     // folding and gathering below read in place
     Tree pTree0 = commit_rows4(x, alg, lEval.p, N / 4, N > 256);                                      // :45-46
 
-    // layers (:176-221): the loop below is the recursion unrolled.  No root is read back inside it: the point every layer folds at,
+    // layers (:176-221), the recursion unrolled.  No root is read back inside it: the point every layer folds at,
     // prng(root of the tree above) (:194), is derived on the device from the root where it lies, so all layers
     // are enqueued without a round trip.  The launch that produces a tree's root also POSTS it to the host and derives that point
     // (gs_merkle_commit_rows_seed): the host picks each root up as soon as its tree exists and derives the layer's query positions and
     // batch-proof plans while the device folds the layers below
     double waited_ms = 0;          // host time blocked on roots that had not arrived yet (the device was the slower side)
-    auto await_root = [&](uint64_t ticket, Tree &t) {
+    auto await_root = [&](Tree &t) {
         const auto w0 = std::chrono::steady_clock::now();
-        x.check(A.gs_readback_wait(x.c, ticket, t.root.data()), "gs_readback_wait(root)");
+        x.check(A.gs_readback_wait(x.c, t.ticket, t.root.data()), "gs_readback_wait(root)");
         waited_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
     };
-    std::vector<uint64_t> tickets;
-    tickets.push_back(pTree0.ticket);
-    std::vector<Layer> layers;
-    Tree *pTree = &pTree0;
-    const void *column_src = lEval.p;   // the current layer's values in natural order (the remainder at the end)
-    uint64_t len = N;
-    uint32_t depth = 0;
-    layers.reserve(32);
-    // every layer's buffers first, then ONE call for the whole recursion (gs_fri_layers = per layer gs_fri_fold_at :189-198 +
-    // gs_merkle_commit_rows_seed :201-202, with as few dependent launches as the sizes allow)
-    while (len > 256) {
-        const uint64_t rows = len / 4;
-        layers.emplace_back();
-        Layer &L = layers.back();
-        L.pTree = pTree;
-        L.column = column_src;
-        L.rows = rows;
-        L.column_length = rows;
-        L.next = Buf(x, rows * ELEM);
-        L.cTree.n = rows / 4;
-        L.cTree.leaves = Buf(x, rows / 4 * DIGEST);
-        L.cTree.nodes = Buf(x, rows / 4 * DIGEST);
-        if (rows > 256) L.cTree.point = Buf(x, ELEM);                                                 // (no layer below the last tree)
-        L.cTree.root.resize(DIGEST);
-        column_src = L.next.p;
-        pTree = &L.cTree;
-        len = rows;
-        depth++;
-    }
-    if (!layers.empty()) {
-        std::vector<gs_fri_layer> outs(layers.size());
-        for (size_t d = 0; d < layers.size(); d++)
-            outs[d] = gs_fri_layer{layers[d].next.p, layers[d].cTree.leaves.p, layers[d].cTree.nodes.p, layers[d].cTree.point.p, 0};
-        le16(omega, s16);
-        x.check(A.gs_fri_layers(x.c, (gs_hash_alg)alg, s16, N, 1, lEval.p, N, pTree0.point.p, (uint32_t)outs.size(), outs.data()), "gs_fri_layers");
-        for (size_t d = 0; d < layers.size(); d++) { layers[d].cTree.ticket = outs[d].ticket; tickets.push_back(outs[d].ticket); }
-    }
+    std::vector<Fold> layers = fri_layers(x, alg, omega, N, 1, lEval.p, N, pTree0.point.p);
     if (layers.size() > 60) fail(GS_ERR_ARG, "too many FRI components");
     clock.mark("FRI layers issued");
     clock.readme(x, "Computed low-degree proof: %zu FRI layers folded and committed", layers.size());
@@ -1276,7 +1335,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     DeferWindow win(x);
     // spot checks of the evaluation tree (lib/Stark.ts:146-152, 274-296) and of the linear combination (LowDegreeProver.ts:52-54,
     // 302-309): positions from the root of the first FRI tree
-    await_root(tickets[0], pTree0);
+    await_root(pTree0);
     const std::vector<uint64_t> exe_positions = plan.exe_positions(pTree0.root), lc_positions = augmented_rows(exe_positions, N);
     MerkleProof lcProof;
     rb.prove_batch(x, pTree0, lc_positions, &lcProof);
@@ -1287,18 +1346,26 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     // the leaves of the evaluation tree are the committed vectors' elements side by side (lib/Stark.ts:284-296)
     std::vector<MerkleProof> cols(V);
     for (uint32_t r = 0; r < V; r++) rb.gather(x, eVectors[r], ELEM, aug, 1, V == 1 ? &evProof : &cols[r]);
-    // queries of every layer (:209-219)
+    // queries of every layer (:209-219): its column (4 * rows values in natural order: rows are read strided, never transposed) under the
+    // tree above, the folded column under its own
+    const Tree *pTree = &pTree0;
+    const void *column = lEval.p;       // the current layer's values (the remainder at the end)
+    uint64_t len = N;
     for (size_t d = 0; d < layers.size(); d++) {
-        Layer &L = layers[d];
-        await_root(tickets[d + 1], L.cTree);
+        Fold &L = layers[d];
+        const uint64_t rows = len / 4;
+        await_root(L.cTree);
         if (d + 1 == layers.size()) clock.mark_split("waiting for FRI roots (device busy)", waited_ms, "query plans while the device folds");
-        const Plan::Queries q = plan.layer_queries(L.cTree.root, L.column_length);
+        const Plan::Queries q = plan.layer_queries(L.cTree.root, rows);
         Component &c = components[d];
         c.columnRoot = L.cTree.root;
         rb.prove_batch(x, L.cTree, q.rows, &c.columnProof);
-        rb.gather_rows4(x, L.next.p, L.column_length / 4, q.rows, &c.columnProof);
-        rb.prove_batch(x, *L.pTree, q.positions, &c.polyProof);
-        rb.gather_rows4(x, L.column, L.rows, q.positions, &c.polyProof);
+        rb.gather_rows4(x, L.next.p, rows / 4, q.rows, &c.columnProof);
+        rb.prove_batch(x, *pTree, q.positions, &c.polyProof);
+        rb.gather_rows4(x, column, rows, q.positions, &c.polyProof);
+        pTree = &L.cTree;
+        column = L.next.p;
+        len = rows;
     }
     if (layers.empty()) clock.mark_split("waiting for FRI roots (device busy)", waited_ms, "query plans while the device folds");
     clock.mark("last root here: the last layer's plan");
@@ -1307,12 +1374,12 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     {
         std::vector<uint64_t> all(len);
         for (uint64_t i = 0; i < len; i++) all[i] = i;
-        x.check(A.gs_gather(x.c, column_src, ELEM, all.data(), len, remainder_raw.data()), "gs_gather(remainder)");
+        x.check(A.gs_gather(x.c, column, ELEM, all.data(), len, remainder_raw.data()), "gs_gather(remainder)");
     }
     win.end();
     clock.mark("remainder + answers fetched (one sync)");
-    for (uint64_t i = 0; i < len; i++) remainder[i] = from16(remainder_raw.data() + ELEM * i);
-    check_remainder(plan, remainder, depth);
+    for (uint64_t i = 0; i < len; i++) remainder[i] = load_elem(remainder_raw.data() + ELEM * i);
+    check_remainder(plan, remainder, (uint32_t)layers.size());
     clock.mark("remainder checked");
     clock.readme(x, "Computed low-degree proof: query answers + Computed %zu evaluation spot checks (one read-back), remainder verified", exe_positions.size());
     if (V > 1) {

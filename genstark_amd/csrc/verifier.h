@@ -211,7 +211,7 @@ void batch_invert(std::vector<F> &v) {
 std::vector<F> run_program(const gs_prover_air &air, const std::vector<F> &cur, const std::vector<F> &nxt, const std::vector<F> &statics) {
     enum { LOADC, LOADR, LOADN, LOADS, ADD, SUB, MUL, POW, POWC, OUT };
     std::vector<F> vm(air.vm_regs ? air.vm_regs : 1, (F)0), out(air.nconstraints, (F)0);
-    auto konst = [&](uint32_t i) { if (i >= air.nconsts) fail(GS_ERR_ARG, "program: constant index out of range"); return from16(air.consts + ELEM * i); };
+    auto konst = [&](uint32_t i) { if (i >= air.nconsts) fail(GS_ERR_ARG, "program: constant index out of range"); return load_elem(air.consts + ELEM * i); };
     auto r = [&](uint32_t i) -> F & { if (i >= vm.size()) fail(GS_ERR_ARG, "program: register out of range"); return vm[i]; };
     for (uint32_t k = 0; k < air.e_ninstr; k++) {
         const uint32_t op = air.e_code[4 * k], d = air.e_code[4 * k + 1], a = air.e_code[4 * k + 2], b = air.e_code[4 * k + 3];
@@ -438,7 +438,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     uint32_t rlen = r.byte();
     if (!rlen) rlen = (uint32_t)MAX_ARRAY;
     std::vector<F> remainder(rlen);
-    for (uint32_t i = 0; i < rlen; i++) remainder[i] = from16(r.take(ELEM));
+    for (uint32_t i = 0; i < rlen; i++) remainder[i] = load_elem(r.take(ELEM));
     // input shapes (lib/Serializer.ts:127-141) — and with them the trace length: the reference sizes the trace from the proof's shapes
     // (initVerificationContext(proof.iShapes, publicInputs), lib/Stark.ts:176).  An AIR without input registers has a fixed trace
     // (job.steps) and a proof of it carries no shapes.
@@ -499,7 +499,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         if (!air.nrc || !air.round_constants) fail(GS_ERR_ARG, "the MiMC AIR needs its round constants");
         if ((air.nrc & (air.nrc - 1)) || T % air.nrc) fail(GS_ERR_ARG, "invalid job: the number of round constants must be a power of two dividing the trace length");
         std::vector<F> rc(air.nrc);
-        for (uint32_t i = 0; i < air.nrc; i++) rc[i] = from16(air.round_constants + ELEM * i);
+        for (uint32_t i = 0; i < air.nrc; i++) rc[i] = load_elem(air.round_constants + ELEM * i);
         static_polys.push_back(cyclic_poly(rc, hf_pow(omega, (hfe)(E * (T / air.nrc)))));
         static_periods.push_back(air.nrc);
     } else {
@@ -530,7 +530,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
                 const uint32_t m = air.static_periods[cyc++];
                 if (!m || (m & (m - 1)) || T % m) fail(GS_ERR_ARG, "a static register's period must be a power of two dividing the trace length");
                 vals.resize(m);
-                for (uint32_t i = 0; i < m; i++) vals[i] = from16(air.static_values + ELEM * (off + i));
+                for (uint32_t i = 0; i < m; i++) vals[i] = load_elem(air.static_values + ELEM * (off + i));
                 off += m;
             } else if (src.kind == GS_STATIC_INPUT || src.kind == GS_STATIC_MASK) {
                 // the column the loader lays out (airassembly.py: _Layout.column / .mask): every value held for `span` steps — or a 1
@@ -549,7 +549,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
                     if (air.inputs[j].secret || public_at[j] < 0) fail(GS_ERR_ARG, "invalid job: static register %u is a public one, input register %u is secret", s, j);
                     const uint8_t *src_vals = air.public_inputs + ELEM * public_off[public_at[j]];
                     for (uint64_t v = 0; v < layout.count[j]; v++) {
-                        const F val = from16(src_vals + ELEM * v);
+                        const F val = load_elem(src_vals + ELEM * v);
                         for (uint64_t i = 0; i < span; i++) vals[v * span + i] = val;
                     }
                 }
@@ -584,8 +584,8 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     auto leaf_values = [&](uint64_t pos, std::vector<F> &p, std::vector<F> &s) {
         const Bytes &b = evProof.values[at_leaf.at(pos)];
         p.resize(R); s.resize(S);
-        for (uint32_t k = 0; k < R; k++) p[k] = from16(b.data() + ELEM * k);
-        for (uint32_t k = 0; k < S; k++) s[k] = from16(b.data() + ELEM * (R + k));
+        for (uint32_t k = 0; k < R; k++) p[k] = load_elem(b.data() + ELEM * k);
+        for (uint32_t k = 0; k < S; k++) s[k] = load_elem(b.data() + ELEM * (R + k));
     };
     if (!merkle_check(alg, evRoot, aug, evProof)) fail(GS_ERR_ARG, "Verification of evaluation Merkle proof failed");
 
@@ -647,7 +647,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
             size_t idx = rows.size();
             for (size_t k = 0; k < rows.size(); k++) if (rows[k] == p % row_len) { idx = k; break; }
             if (idx >= mp.values.size()) fail(GS_ERR_ARG, "malformed proof: a queried row is missing");
-            out.push_back(from16(mp.values[idx].data() + ELEM * (p / row_len)));
+            out.push_back(load_elem(mp.values[idx].data() + ELEM * (p / row_len)));
         }
         return out;
     };
@@ -682,7 +682,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         for (size_t i = 0; i < pos.size(); i++) {
             const F xinv = hf_pow(rou, (hfe)((domain_size - pos[i]) % domain_size));
             F y[4];
-            for (int k = 0; k < 4; k++) y[k] = from16(c.polyProof.values[i].data() + ELEM * k);
+            for (int k = 0; k < 4; k++) y[k] = load_elem(c.polyProof.values[i].data() + ELEM * k);
             const F s0 = hf_add(y[0], y[2]), s1 = hf_sub(y[0], y[2]), s2 = hf_add(y[1], y[3]), s3 = hf_mul(hf_sub(y[1], y[3]), zeta[3]);     // zeta^-1 = zeta^3
             const F u0 = hf_add(s0, s2), u2 = hf_sub(s0, s2), u1 = hf_add(s1, s3), u3 = hf_sub(s1, s3);
             const F t = hf_mul(special, xinv);
@@ -710,7 +710,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         std::vector<Bytes> level(rows, Bytes(32));
         for (uint64_t i = 0; i < rows; i++) {
             uint8_t msg[4 * GS_PROVER_ELT_MAX];
-            for (int k = 0; k < 4; k++) le16(remainder[i + k * rows], msg + ELEM * k);
+            for (int k = 0; k < 4; k++) store_elem(remainder[i + k * rows], msg + ELEM * k);
             host_digest(alg, msg, 4 * ELEM, level[i].data());
         }
         if (rows & (rows - 1)) fail(GS_ERR_ARG, "malformed proof: remainder length");
@@ -747,15 +747,15 @@ static int boundary_at_entry(const uint8_t *omega, uint64_t n, uint64_t steps, c
     if (!steps || (steps & (steps - 1)) || !n || (n & (n - 1)) || n < steps) return GS_ERR_ARG;
     return guarded(err, errcap, GS_ERR_OOM, [&]() -> int {
         Plan plan;
-        plan.T = steps; plan.N = n; plan.E = n / steps; plan.omega = from16(omega);
+        plan.T = steps; plan.N = n; plan.E = n / steps; plan.omega = load_elem(omega);
         plan.regs.push_back(Plan::Reg{0, {}, {}, {}});
         Plan::Reg &r = plan.regs[0];
-        for (uint32_t i = 0; i < m; i++) { r.steps.push_back(at[i]); r.ys.push_back(from16(values + ELEM * i)); }
+        for (uint32_t i = 0; i < m; i++) { r.steps.push_back(at[i]); r.ys.push_back(load_elem(values + ELEM * i)); }
         plan.fill_xs();
         std::vector<F> pts(npoints);
-        for (uint32_t q = 0; q < npoints; q++) pts[q] = from16(points + ELEM * q);
+        for (uint32_t q = 0; q < npoints; q++) pts[q] = load_elem(points + ELEM * q);
         const BoundaryValues bv = method ? boundary_values_tree(plan, r, pts) : boundary_values_direct(plan, r, pts);
-        for (uint32_t q = 0; q < npoints; q++) { le16(bv.i_at[q], i_out + ELEM * q); le16(bv.z_at[q], z_out + ELEM * q); }
+        for (uint32_t q = 0; q < npoints; q++) { store_elem(bv.i_at[q], i_out + ELEM * q); store_elem(bv.z_at[q], z_out + ELEM * q); }
         return GS_OK;
     });
 }

@@ -413,3 +413,33 @@ def test_native_prover_mixed_constraint_degrees(oracle_backend, degrees):
     want = stark.serialize(stark.prove(assertions, [], [42, 43]))
     assert NativeProver(stark).prove_bytes(assertions, [], [42, 43]) == want
     assert stark.verify(assertions, stark.parse(want))
+
+
+def mimc_above_the_cap(backend, log_t, ef, alg='blake2s256'):
+    """A MiMC statement at an extension factor above 32.  Every host refuses one (README.md:112; MimcAir, GenericAir and the JS loaders
+    enforce it), the job format and the drivers do not: the AIR is made at 32 and its factor raised before anything is derived from it.
+    Five assertions on register 0: neither gs_mimc_composition nor gs_composition_tail takes them."""
+    from genstark_amd.air import MimcAir
+    steps = 1 << log_t
+
+    def mk(be):
+        air = MimcAir(steps, 32, PrimeField(backend=be))
+        air.extensionFactor = ef
+        return Stark(air, {'hashAlgorithm': alg, 'extensionFactor': ef, 'exeQueryCount': 40, 'friQueryCount': 24})
+    stark = mk(backend)
+    controls = ga.runMimc(stark.air.field, steps, stark.air.roundConstants, 3)
+    assertions = [{'step': s, 'register': 0, 'value': controls[s]} for s in (0, 5, steps // 2, 77 % steps, steps - 1)]
+    return mk, stark, [3], assertions
+
+
+def test_native_prover_extension_factor_64_takes_the_general_zero_polynomial(oracle_backend):
+    """E = 64: x^T - 1 takes more values than gs_zero_poly_inverses tabulates, so 1/Z(x) comes from the general vector sequence
+    (gs_power_series, gs_pluck, gs_vec_sub_scalar, gs_vec_div: ZeroPolynomial.ts:36-44 as written) — reachable by a raw caller of
+    gs_prover_prove only.  Same bytes as the mirror, which evaluates Z(x) the reference's way; the native verifier accepts them."""
+    _, stark, seed, assertions = mimc_above_the_cap(oracle_backend, 7, 64)
+    want = stark.serialize(stark.prove(assertions, [], seed))
+    native = NativeProver(stark)
+    got = native.prove_bytes(assertions, [], seed)
+    assert got == want
+    assert native.verify_bytes(assertions, got) is True
+    assert stark.verify(assertions, stark.parse(got))
