@@ -134,6 +134,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _OPTIONAL_SIGNATURES = {
     'gs_boundary_polys': (_int, [_vp, _bytes, _u64, _u64, C.POINTER(_u64), _bytes, C.POINTER(_u32), _u32, _u32, _vp, _vp]),
     'gs_boundary_schoolbook_log2': (_u32, [_u32]),
+    'gs_eval_polys_at_points': (_int, [_vp, _vp, _u32, _u64, C.POINTER(_u64), _bytes, _u32, _vp]),
+    'gs_eval_polys_at_points_segment': (_u32, []),
 }
 OPTIONAL_SYMBOLS = tuple(_OPTIONAL_SIGNATURES)
 

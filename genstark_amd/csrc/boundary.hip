@@ -105,6 +105,80 @@ __global__ __launch_bounds__(256) void k_bd_take(const fe *__restrict__ prod, co
     }
 }
 
+// ---- many polynomials at many ARBITRARY points (gs_eval_polys_at_points): what a verifier needs of I_r, Z_r and the columns of public
+// input registers — their values at the <= 128 queried points, which are no roots of a transform.  One workgroup per (row, block of
+// GS_EP_POINTS points, segment of GS_EP_SEGMENT coefficients): thread t runs Horner in y = x^256 over the coefficients = t (mod 256) of
+// its segment (lanes read neighbouring coefficients, every coefficient loaded serves all points of the block), then
+//   sum_t x^t a_t   is folded through LDS: a_t += x^h a_(t+h) for h = 128, 64, .. 1 — the powers x^(2^k) are the squarings that lead to y.
+// A second small launch combines the segments (Horner in x^GS_EP_SEGMENT).  Field addition is exact: the value does not depend on how
+// the sum is split, so neither on these two constants.
+#define GS_EP_POINTS 4
+#define GS_EP_SEGMENT 4096
+__global__ __launch_bounds__(256) void k_eval_points_partial(const fe *__restrict__ polys, uint64_t stride, const uint64_t *__restrict__ lens,
+                                                             const fe *__restrict__ points, uint32_t npoints, uint32_t nseg, fe *__restrict__ partial) {
+    __shared__ fe xp[GS_EP_POINTS][9];                           // x^(2^k), k = 0 .. 8
+    __shared__ fe red[GS_EP_POINTS][256];
+    const uint32_t t = threadIdx.x, seg = blockIdx.x, pb = blockIdx.y, r = blockIdx.z;
+    const uint64_t len = lens[r], start = (uint64_t)seg * GS_EP_SEGMENT;
+    if (start >= len) return;                                    // (the whole workgroup: the combining launch reads the segments of `len` only)
+    const uint64_t count = len - start < GS_EP_SEGMENT ? len - start : GS_EP_SEGMENT;
+    if (t < GS_EP_POINTS) {
+        const uint32_t k = pb * GS_EP_POINTS + t;
+        fe x = k < npoints ? points[k] : fe_zero();
+        for (int j = 0; j < 8; j++) { xp[t][j] = x; x = fe_mul(x, x); }
+        xp[t][8] = x;
+    }
+    __syncthreads();
+    fe y[GS_EP_POINTS], acc[GS_EP_POINTS];
+#pragma unroll
+    for (int p = 0; p < GS_EP_POINTS; p++) { y[p] = xp[p][8]; acc[p] = fe_zero(); }
+    const fe *row = polys + (uint64_t)r * stride + start;
+    // coefficients t, t + 256, ...: the highest first
+    if (t < count) {
+#pragma unroll 1
+        for (int64_t i = (int64_t)(t + ((count - 1 - t) & ~255ull)); i >= 0; i -= 256) {
+            const fe c = row[i];
+#pragma unroll
+            for (int p = 0; p < GS_EP_POINTS; p++) acc[p] = fe_add(fe_mul(acc[p], y[p]), c);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < GS_EP_POINTS; p++) red[p][t] = acc[p];
+    __syncthreads();
+    int k = 7;
+#pragma unroll 1
+    for (uint32_t h = 128; h >= 1; h >>= 1, k--) {
+        if (t < h) {
+#pragma unroll
+            for (int p = 0; p < GS_EP_POINTS; p++) red[p][t] = fe_add(red[p][t], fe_mul(red[p][t + h], xp[p][k]));
+        }
+        __syncthreads();
+    }
+    if (t < GS_EP_POINTS) {
+        const uint32_t q = pb * GS_EP_POINTS + t;
+        if (q < npoints) partial[((uint64_t)r * nseg + seg) * npoints + q] = red[t][0];
+    }
+}
+// out[r][k] = sum_s partial[r][s][k] x_k^(s * GS_EP_SEGMENT) over the segments row r has (none: 0)
+__global__ __launch_bounds__(256) void k_eval_points_combine(const fe *__restrict__ partial, const uint64_t *__restrict__ lens, const fe *__restrict__ points,
+                                                             uint32_t rows, uint32_t npoints, uint32_t nseg, fe *__restrict__ out) {
+    const uint64_t total = (uint64_t)rows * npoints;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = i / npoints, k = i % npoints;
+        const uint64_t segs = (lens[r] + GS_EP_SEGMENT - 1) / GS_EP_SEGMENT;
+        fe acc = fe_zero();
+        if (segs) {
+            const fe *col = partial + r * nseg * npoints + k;
+            acc = col[(segs - 1) * npoints];
+            if (segs > 1) {
+                const fe z = fe_pow_u64(points[k], GS_EP_SEGMENT);
+                for (uint64_t s = segs - 1; s-- > 0;) acc = fe_add(fe_mul(acc, z), col[s * npoints]);
+            }
+        }
+        out[i] = acc;
+    }
+}
+
 namespace {
 
 // device blocks of one call, returned to the context's cache on every way out
@@ -253,6 +327,48 @@ int gs_boundary_polys(gs_ctx *c, const gs_elt *omega_bytes, uint64_t n, uint64_t
     if ((rc = interpolate_rows(c, ez, rows, w2t, 2 * T, ew))) return rc;
     hipLaunchKernelGGL(k_bd_take, dim3(gs_grid((uint64_t)rows * (width + 1ull))), dim3(256), 0, c->stream, ew, z, d_per_row, rows, width, T, W, (fe *)i_out,
                        (fe *)z_out);
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
+
+uint32_t gs_eval_polys_at_points_segment(void) { return GS_EP_SEGMENT; }
+
+int gs_eval_polys_at_points(gs_ctx *c, const void *polys, uint32_t rows, uint64_t stride, const uint64_t *lens_host, const uint8_t *points_host, uint32_t npoints,
+                            void *out) {
+    if (!c || !lens_host || (npoints && !points_host) || ((uint64_t)rows * npoints && !out)) return GS_ERR_ARG;
+    if (!rows || !npoints) return GS_OK;
+    if (rows > 65535) return gs_fail(c, GS_ERR_ARG, "eval_polys_at_points: at most 65535 rows per call");
+    if (stride > (1ull << 40) || (rows > 1 && !stride)) return gs_fail(c, GS_ERR_ARG, "eval_polys_at_points: rows of 1 .. 2^40 elements");
+    uint64_t longest = 0;
+    for (uint32_t r = 0; r < rows; r++) {
+        if (lens_host[r] > stride) return gs_fail(c, GS_ERR_ARG, "eval_polys_at_points: row %u has %llu coefficients, the rows are %llu apart", r,
+                                                  (unsigned long long)lens_host[r], (unsigned long long)stride);
+        if (lens_host[r] > longest) longest = lens_host[r];
+    }
+    if (longest && !polys) return GS_ERR_ARG;
+    const uint64_t nseg = (longest + GS_EP_SEGMENT - 1) / GS_EP_SEGMENT, pblocks = ((uint64_t)npoints + GS_EP_POINTS - 1) / GS_EP_POINTS;
+    if (pblocks > 65535) return gs_fail(c, GS_ERR_ARG, "eval_polys_at_points: at most %u points per call", 65535u * GS_EP_POINTS);
+    Blocks blocks(c);
+    void *p;
+    int rc;
+    if ((rc = blocks.get(rows * 8ull, &p))) return rc;
+    uint64_t *d_lens = (uint64_t *)p;
+    if ((rc = blocks.get((uint64_t)npoints * GS_ELT, &p))) return rc;
+    fe *d_points = (fe *)p;
+    if ((rc = blocks.get((uint64_t)rows * nseg * npoints * GS_ELT, &p))) return rc;
+    fe *partial = (fe *)p;
+    if ((rc = gs_push(c, d_lens, lens_host, rows * 8ull))) return rc;
+    if ((rc = gs_push(c, d_points, points_host, (uint64_t)npoints * GS_ELT))) return rc;
+    if (nseg) {
+        uint64_t coefficients = 0;
+        for (uint32_t r = 0; r < rows; r++) coefficients += lens_host[r];
+        gs_traffic(c, (coefficients * pblocks + (uint64_t)rows * nseg * npoints) * GS_ELT, coefficients * npoints, "k_eval_points_partial");
+        hipLaunchKernelGGL(k_eval_points_partial, dim3((unsigned)nseg, (unsigned)pblocks, rows), dim3(256), 0, c->stream, (const fe *)polys, stride, d_lens, d_points,
+                           npoints, (uint32_t)nseg, partial);
+        GS_LAUNCH_CHECK(c);
+    }
+    hipLaunchKernelGGL(k_eval_points_combine, dim3(gs_grid((uint64_t)rows * npoints)), dim3(256), 0, c->stream, partial, d_lens, d_points, rows, npoints,
+                       (uint32_t)nseg, (fe *)out);
     GS_LAUNCH_CHECK(c);
     return GS_OK;
 }

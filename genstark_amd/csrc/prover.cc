@@ -1,6 +1,6 @@
 // prover.cc — the whole of Stark.prove() (lib/Stark.ts:81-163) as NATIVE host code above the C ABI.
 //
-// The Python package mirrors lib/Stark.ts and lib/components/*.ts call by call (genstark_amd/stark.py, components/); that
+// The Python package mirrors lib/Stark.ts and lib/components/*.ts call by call (genstark_amd/_mirror/stark.py, _mirror/components/); that
 // mirror is the readable reference for the sequence below and stays the thing the parity tests compare against.  This file
 // is the same sequence — context set-up, trace, P(x), low-degree extension, evaluation tree, CompositionPolynomial
 // (CompositionPolynomial.ts:29-146, BoundaryConstraints.ts:15-95, ZeroPolynomial.ts:36-44), LinearCombination (:36-64),
@@ -47,7 +47,7 @@ namespace {
     X(gs_air_trace_segments) X(gs_air_constraints) X(gs_air_constraints_strided) X(gs_composition_tail) X(gs_composition_tail_coset) X(gs_zero_poly_inverses) X(gs_div_by_domain_roots) X(gs_mimc_composition) X(gs_fri_fold) X(gs_fri_fold_seeded) X(gs_defer_begin) X(gs_defer_end) X(gs_readback_post) X(gs_readback_wait) X(gs_merkle_commit_rows_seed) X(gs_fri_fold_at) \
     X(gs_vec_mul_scalar) X(gs_copy) X(gs_gather_words) X(gs_transpose_records) X(gs_fri_fold_seeded_scaled) X(gs_fri_layers) X(gs_sync) X(gs_zero_poly_inverses_coset) X(gs_div_by_domain_roots_coset)
 // ... and the entry points an implementation may lack (include/gstark_boundary.h): null then, and the driver keeps its host path
-#define GS_API_OPTIONAL_LIST(X) X(gs_boundary_polys)
+#define GS_API_OPTIONAL_LIST(X) X(gs_boundary_polys) X(gs_eval_polys_at_points)
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
     GS_API_LIST(X)

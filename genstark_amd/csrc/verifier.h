@@ -375,18 +375,22 @@ BoundaryValues boundary_values_direct(const Plan &plan, const Plan::Reg &r, cons
     for (F x : points) { out.i_at.push_back(horner(ipoly, x)); out.z_at.push_back(horner(zpoly, x)); }
     return out;
 }
-BoundaryValues boundary_values_tree(const Plan &plan, const Plan::Reg &r, const std::vector<F> &points) {
+// what the tree form refuses of a register's assertions, with its messages
+void check_many_assertions(const Plan &plan, const Plan::Reg &r) {
     const size_t m = r.steps.size();
     const uint64_t T = plan.T;
     if (m > T) fail(GS_ERR_ARG, "Invalid assertion: register %u has %zu assertions, the execution trace %llu steps", r.reg, m, (unsigned long long)T);
-    {
-        std::vector<bool> seen(T, false);
-        for (uint64_t s : r.steps) {
-            if (s >= T) fail(GS_ERR_ARG, "Invalid assertion: step %llu is outside of execution trace", (unsigned long long)s);
-            if (seen[s]) fail(GS_ERR_ARG, "Invalid assertion: step %llu of register %u is asserted more than once", (unsigned long long)s, r.reg);
-            seen[s] = true;
-        }
+    std::vector<bool> seen(T, false);
+    for (uint64_t s : r.steps) {
+        if (s >= T) fail(GS_ERR_ARG, "Invalid assertion: step %llu is outside of execution trace", (unsigned long long)s);
+        if (seen[s]) fail(GS_ERR_ARG, "Invalid assertion: step %llu of register %u is asserted more than once", (unsigned long long)s, r.reg);
+        seen[s] = true;
     }
+}
+BoundaryValues boundary_values_tree(const Plan &plan, const Plan::Reg &r, const std::vector<F> &points) {
+    const size_t m = r.steps.size();
+    const uint64_t T = plan.T;
+    check_many_assertions(plan, r);
     const std::vector<F> z = zero_poly_tree(r.xs.data(), m, plan.omega, plan.N);
     std::vector<F> d(T, (F)0);                                       // Z_r' ...
     for (size_t k = 0; k < m; k++) d[k] = vf_mul((F)(uint64_t)(k + 1), z[k + 1]);
@@ -408,7 +412,101 @@ BoundaryValues boundary_values_tree(const Plan &plan, const Plan::Reg &r, const 
     return out;
 }
 
-void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_len) {
+
+// ---- the device's share of a device-assisted verification (gs_prover_verify_device).  Two providers of "values at the queried points"
+// are all that differs from verify_impl's host form, and only for LONG polynomials:
+//   I_r, Z_r of a register with more than `min_assertions` assertions: their coefficients from gs_boundary_polys (what prove() builds
+//            them with), evaluated by gs_eval_polys_at_points — instead of boundary_values_tree (a host product tree, a T-point host
+//            transform and m barycentric terms per point);
+//   the column of a public input register whose shortest period exceeds `min_column`: uploaded, gs_interpolate_roots,
+//            gs_eval_polys_at_points — instead of cyclic_poly + horner_many.
+// Both are the same field elements (unique polynomials, exact arithmetic), read back with ONE gs_download.  Whatever the host form
+// refuses of a statement is refused here first, with its message, before anything is enqueued.
+struct DeviceVerify {
+    gs_ctx *c;
+    size_t min_assertions;
+    uint64_t min_column;
+};
+struct DeviceColumn { size_t at; std::vector<F> values; };      // static register `at`: one period of its column
+// may the device build this register's boundary polynomials?  (Throws what the host form would throw of it.)
+bool device_boundary_fits(const Plan &plan, const Plan::Reg &r) {
+    if (plan.E < 2 || plan.T > (1ull << 28)) return false;          // gs_boundary_polys: a domain of at least 2 T points, T <= 2^28
+    if (r.steps.size() > BOUNDARY_DIRECT_MAX) { check_many_assertions(plan, r); return true; }
+    // (below BOUNDARY_DIRECT_MAX — reached with the thresholds lowered — the host's direct form is the judge of a repeated step)
+    std::vector<uint64_t> sorted(r.steps);
+    std::sort(sorted.begin(), sorted.end());
+    return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end() && sorted.back() < plan.T;
+}
+void device_values(const DeviceVerify &dev, const Plan &plan, const std::vector<F> &points, const std::vector<size_t> &regs, std::vector<BoundaryValues> &bvals,
+                   const std::vector<DeviceColumn> &columns, std::vector<std::vector<F>> &column_values) {
+    Ctx x{dev.c};
+    const uint32_t Q = (uint32_t)points.size(), nb = (uint32_t)regs.size();
+    column_values.assign(columns.size(), std::vector<F>());
+    if (!Q) return;
+    auto evaluate = [&](const void *polys, uint32_t rows, uint64_t stride, const std::vector<uint64_t> &lens, const Bytes &at, void *out) {
+        x.check(A.gs_eval_polys_at_points(x.c, polys, rows, stride, lens.data(), at.data(), Q, out), "gs_eval_polys_at_points");
+    };
+    Buf out(x, (2ull * nb + columns.size()) * Q * ELEM);
+    Buf iPolys, zPolys;
+    if (nb) {
+        uint32_t width = 0;
+        for (size_t k : regs) width = std::max(width, (uint32_t)plan.regs[k].steps.size());
+        std::vector<uint64_t> at((size_t)nb * width, 0), ilen(nb), zlen(nb);
+        std::vector<uint32_t> per_row(nb);
+        Bytes ys((size_t)nb * width * ELEM, 0);
+        for (uint32_t r = 0; r < nb; r++) {
+            const Plan::Reg &d = plan.regs[regs[r]];
+            per_row[r] = (uint32_t)d.steps.size(); ilen[r] = d.steps.size(); zlen[r] = d.steps.size() + 1;
+            for (size_t k = 0; k < d.steps.size(); k++) {
+                at[(size_t)r * width + k] = d.steps[k];
+                store_elem(d.ys[k], ys.data() + ((size_t)r * width + k) * ELEM);
+            }
+        }
+        iPolys = Buf(x, (uint64_t)nb * width * ELEM);
+        zPolys = Buf(x, (uint64_t)nb * (width + 1ull) * ELEM);
+        x.check(A.gs_boundary_polys(x.c, enc(plan.omega), plan.N, plan.T, at.data(), ys.data(), per_row.data(), nb, width, iPolys.p, zPolys.p), "gs_boundary_polys");
+        const Bytes pts = pack(points, 0, Q);
+        evaluate(iPolys.p, nb, width, ilen, pts, out.p);
+        evaluate(zPolys.p, nb, width + 1ull, zlen, pts, out.at((uint64_t)nb * Q * ELEM));
+    }
+    // columns of one period share an upload, a transform, their points x^(T / period) and an evaluation
+    std::map<uint64_t, std::vector<size_t>> by_period;
+    for (size_t k = 0; k < columns.size(); k++) by_period[columns[k].values.size()].push_back(k);
+    std::vector<uint64_t> row_of(columns.size());
+    uint64_t row = 2ull * nb;
+    std::vector<Buf> held;
+    for (auto &g : by_period) {
+        const uint64_t m = g.first;
+        const uint32_t cnt = (uint32_t)g.second.size();
+        Bytes host(cnt * m * ELEM);
+        for (uint32_t j = 0; j < cnt; j++) {
+            const std::vector<F> &v = columns[g.second[j]].values;
+            for (uint64_t i = 0; i < m; i++) store_elem(v[i], host.data() + (j * m + i) * ELEM);
+            row_of[g.second[j]] = row + j;
+        }
+        held.emplace_back(x, host.size());
+        held.emplace_back(x, host.size());
+        Buf &ys = held[held.size() - 2], &poly = held.back();
+        x.check(A.gs_upload(x.c, ys.p, host.data(), host.size()), "gs_upload(input register columns)");
+        x.check(A.gs_interpolate_roots(x.c, ys.p, cnt, enc(hf_pow(plan.omega, (hfe)(plan.E * (plan.T / m)))), m, poly.p), "gs_interpolate_roots(input register columns)");
+        std::vector<F> at(Q);
+        for (uint32_t q = 0; q < Q; q++) at[q] = hf_pow(points[q], (hfe)(plan.T / m));
+        evaluate(poly.p, cnt, m, std::vector<uint64_t>(cnt, m), pack(at, 0, Q), out.at(row * Q * ELEM));
+        row += cnt;
+    }
+    Bytes back((size_t)row * Q * ELEM);
+    x.check(A.gs_download(x.c, back.data(), out.p, back.size()), "gs_download(values at the queried points)");
+    auto take = [&](uint64_t r) {
+        std::vector<F> v(Q);
+        for (uint32_t q = 0; q < Q; q++) v[q] = load_elem(back.data() + (r * Q + q) * ELEM);
+        return v;
+    };
+    for (uint32_t r = 0; r < nb; r++) { bvals[regs[r]].i_at = take(r); bvals[regs[r]].z_at = take((uint64_t)nb + r); }
+    for (size_t k = 0; k < columns.size(); k++) column_values[k] = take(row_of[k]);
+}
+
+// dev = null: everything on this host core (gs_prover_verify)
+void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_len, const DeviceVerify *dev) {
     const gs_prover_air &air = job.air;
     const uint64_t E = job.extension_factor;
     const uint32_t R = air.registers, S = air.nsecret;
@@ -468,7 +566,9 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     if (T > (1ull << 32) / E) fail(GS_ERR_ARG, "a trace of %llu steps at extension factor %llu is beyond this verifier", (unsigned long long)T, (unsigned long long)E);
     const uint64_t N = T * E;
     const F omega = domain_root(job, N);
-    const Plan plan = make_plan(job, T, E, omega);
+    // (the assertions' points are what the HOST forms of the boundary values work on: with a device they wait for the first register that needs them)
+    Plan plan = make_plan(job, T, E, omega, dev == nullptr);
+    bool have_xs = dev == nullptr;
     const uint64_t combination_degree = plan.combination_degree, b_inc = plan.b_inc;
     // the number of FRI layers is a function of the domain size alone (LowDegreeProver.ts:179: fold while more than 256 values are
     // left); a proof with any other count is malformed — in particular one with extra layers, which would floor the degree bound of
@@ -495,6 +595,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     // static registers of the AIR at a point (kind 1: K_s(x^(T/period)); kind 0: the round-constant register)
     std::vector<std::vector<F>> static_polys;
     std::vector<uint64_t> static_periods;
+    std::vector<DeviceColumn> device_columns;                                 // (their entries of static_polys stay empty)
     if (air.kind == 0) {
         if (!air.nrc || !air.round_constants) fail(GS_ERR_ARG, "the MiMC AIR needs its round constants");
         if ((air.nrc & (air.nrc - 1)) || T % air.nrc) fail(GS_ERR_ARG, "invalid job: the number of round constants must be a power of two dividing the trace length");
@@ -559,7 +660,12 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
                 fail(GS_ERR_ARG, "invalid job: static register %u has unknown source %u", s, src.kind);
             }
             const uint64_t m = vals.size();
-            static_polys.push_back(cyclic_poly(vals, hf_pow(omega, (hfe)(E * (T / m)))));
+            if (dev && src.kind == GS_STATIC_INPUT && m > dev->min_column) {
+                device_columns.push_back(DeviceColumn{static_polys.size(), std::move(vals)});
+                static_polys.emplace_back();
+            } else {
+                static_polys.push_back(cyclic_poly(vals, hf_pow(omega, (hfe)(E * (T / m)))));
+            }
             static_periods.push_back(m);
         }
     }
@@ -595,13 +701,22 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
     std::vector<F> lcValues, xsq, dens;
     for (uint64_t step : positions) xsq.push_back(hf_pow(omega, (hfe)step));
     std::vector<BoundaryValues> bvals;                                    // per asserted register: I_r and Z_r at every queried point (BoundaryConstraints.ts:42, :24-30)
-    for (auto &d : rdata) bvals.push_back(d.steps.size() <= BOUNDARY_DIRECT_MAX ? boundary_values_direct(plan, d, xsq) : boundary_values_tree(plan, d, xsq));
+    std::vector<size_t> device_regs;                                      // ... of these the device provides them (filled in below)
+    for (size_t k = 0; k < rdata.size(); k++) {
+        const Plan::Reg &d = rdata[k];
+        if (dev && d.steps.size() > dev->min_assertions && device_boundary_fits(plan, d)) { device_regs.push_back(k); bvals.emplace_back(); continue; }
+        if (!have_xs) { plan.fill_xs(); have_xs = true; }
+        bvals.push_back(d.steps.size() <= BOUNDARY_DIRECT_MAX ? boundary_values_direct(plan, d, xsq) : boundary_values_tree(plan, d, xsq));
+    }
+    std::vector<std::vector<F>> device_column_values;
+    if (dev && (!device_regs.empty() || !device_columns.empty())) device_values(*dev, plan, xsq, device_regs, bvals, device_columns, device_column_values);
     for (size_t pi = 0; pi < positions.size(); pi++) {
         dens.push_back(hf_sub(hf_pow(xsq[pi], (hfe)T), 1));                                            // ZeroPolynomial.ts:28-34: Z = (x^T - 1) / (x - x_last)
         for (auto &bv : bvals) dens.push_back(bv.z_at[pi]);                                         // BoundaryConstraints.ts:55-69
     }
     batch_invert(dens);
-    for (size_t k = 0; k < static_polys.size(); k++) {                        // K_s(x^(T/period)) at every queried x
+    for (size_t k = 0, dc = 0; k < static_polys.size(); k++) {                // K_s(x^(T/period)) at every queried x
+        if (dc < device_columns.size() && device_columns[dc].at == k) { statics_at.push_back(std::move(device_column_values[dc++])); continue; }
         std::vector<F> at(xsq.size());
         for (size_t pi = 0; pi < xsq.size(); pi++) at[pi] = hf_pow(xsq[pi], (hfe)(T / static_periods[k]));
         statics_at.push_back(horner_many(static_polys[k], at));
@@ -736,7 +851,23 @@ extern "C" {
 static int verify_entry(const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap) {
     if (!job || !proof) return GS_ERR_ARG;
     return guarded(err, errcap, GS_ERR_ARG, [&]() -> int {
-        verify_impl(*job, proof, len);
+        verify_impl(*job, proof, len, nullptr);
+        return GS_OK;
+    });
+}
+// Thresholds of the device providers.  Measured (tools/verify_device_bench.py, profiles/verify_device.md): NOT YET — the values below are
+// where the host's own forms change (BOUNDARY_DIRECT_MAX) and an estimate for the columns.
+const uint32_t VERIFY_DEVICE_MIN_ASSERTIONS = 256;
+const uint64_t VERIFY_DEVICE_MIN_COLUMN = 1024;
+static thread_local uint32_t g_verify_min_assertions = 0;      // gs_prover_verify_device_min: 0 = the default
+static thread_local uint64_t g_verify_min_column = 0;
+static int verify_device_entry(gs_ctx *ctx, const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap) {
+    if (!ctx || !job || !proof) return GS_ERR_ARG;
+    return guarded(err, errcap, GS_ERR_ARG, [&]() -> int {
+        const DeviceVerify dev{ctx, g_verify_min_assertions ? g_verify_min_assertions : VERIFY_DEVICE_MIN_ASSERTIONS,
+                               g_verify_min_column ? g_verify_min_column : VERIFY_DEVICE_MIN_COLUMN};
+        // a library without the two optional entries (a test double): the host providers answer
+        verify_impl(*job, proof, len, A.gs_boundary_polys && A.gs_eval_polys_at_points ? &dev : nullptr);
         return GS_OK;
     });
 }
@@ -775,5 +906,17 @@ int gs_prover_verify_on(const gs_prover_binding *b, const struct gs_prover_job *
     UseApi use(reinterpret_cast<const Api *>(b));
     return verify_entry(job, proof, len, err, errcap);
 }
+int gs_prover_verify_device(gs_ctx *ctx, const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap) {
+    if (!g_bound) return GS_ERR_UNSUPPORTED;
+    UseApi use(&g_default_api);
+    return verify_device_entry(ctx, job, proof, len, err, errcap);
+}
+int gs_prover_verify_device_on(const gs_prover_binding *b, gs_ctx *ctx, const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err,
+                               uint64_t errcap) {
+    if (!b) return GS_ERR_ARG;
+    UseApi use(reinterpret_cast<const Api *>(b));
+    return verify_device_entry(ctx, job, proof, len, err, errcap);
+}
+void gs_prover_verify_device_min(uint32_t assertions, uint64_t column) { g_verify_min_assertions = assertions; g_verify_min_column = column; }
 
 }  // extern "C"

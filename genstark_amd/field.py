@@ -395,6 +395,31 @@ class PrimeField:
         self.backend.call('gs_eval_poly_at', C.c_void_p(poly.ptr), poly.length, self.le(x), C.cast(buf, C.c_void_p))
         return int.from_bytes(buf.raw, 'little')
 
+    def evalPolysAtPoints(self, polys, xs):
+        """The rows of `polys` (a Matrix of coefficients, or a list of Vectors) at every x of `xs` (integers; any points, not roots of a
+        transform): a Matrix, [r][k] = p_r(xs[k]).  One launch and no read-back where the library has gs_eval_polys_at_points
+        (include/gstark_boundary.h); one evalPolyAt per polynomial and point on a library without it."""
+        xs = [x % self.modulus for x in xs]
+        rows = [polys.row(r) for r in range(polys.rowCount)] if isinstance(polys, Matrix) else list(polys)
+        out = Matrix(self.backend, len(rows), len(xs))
+        if not rows or not xs:
+            return out
+        if not hasattr(self.backend.lib, 'gs_eval_polys_at_points'):
+            values = b''.join(self.le(self.evalPolyAt(p, x)) for p in rows for x in xs)
+            self.backend.upload(out.ptr, values)
+            return out
+        if isinstance(polys, Matrix):
+            src, stride, lens = polys, polys.colCount, [polys.colCount] * len(rows)
+        else:       # vectors of any lengths, side by side in rows of the longest
+            stride, lens = max(p.length for p in rows), [p.length for p in rows]
+            src = Matrix(self.backend, len(rows), max(stride, 1))
+            for r, p in enumerate(rows):
+                if p.length:
+                    self.backend.call('gs_copy', C.c_void_p(src.ptr + r * stride * self.elementSize), C.c_void_p(p.ptr), p.length * self.elementSize)
+        self.backend.call('gs_eval_polys_at_points', C.c_void_p(src.ptr), len(rows), stride, (C.c_uint64 * len(rows))(*lens),
+                          b''.join(self.le(x) for x in xs), len(xs), C.c_void_p(out.ptr))
+        return out
+
     def mulPolys(self, a, b):
         """BoundaryConstraints.ts:30 — product of two polynomials.  The reference only multiplies tiny ones (degree <= number
         of assertions): those stay on the host; larger operands go through the device NTT (evaluate both on a domain of

@@ -104,6 +104,10 @@ def _driver(backend):
             lib.gs_prover_prove_on.restype = C.c_int
             lib.gs_prover_verify_on.argtypes = [C.c_void_p, C.POINTER(_Job), C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
             lib.gs_prover_verify_on.restype = C.c_int
+            lib.gs_prover_verify_device_on.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Job), C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
+            lib.gs_prover_verify_device_on.restype = C.c_int
+            lib.gs_prover_verify_device_min.argtypes = [C.c_uint32, C.c_uint64]
+            lib.gs_prover_verify_device_min.restype = None
             lib.gs_prover_last_stats.argtypes = [C.POINTER(_Stats)]
             lib.gs_prover_last_stats.restype = C.c_int
             lib.gs_prover_sync_phases.argtypes = [C.c_int]
@@ -323,11 +327,28 @@ class NativeProver:
             raise StarkError(f'native prove() failed ({rc}): {err.value.decode(errors="replace")}')
         return C.string_at(out, n.value)
 
-    def verify_bytes(self, assertions, data, publicInputs=None):
+    def verify_bytes(self, assertions, data, publicInputs=None, device=False):
         """Stark.verify(assertions, stark.parse(data), publicInputs) natively (csrc/verifier.h: lib/Stark.ts:167-248 +
-        LowDegreeProver.ts:70-172 on host scalars, no device work): True, or StarkError with the reference's message.  For an
+        LowDegreeProver.ts:70-172 on host scalars, no device work): True, or StarkError with the reference's message.
+        device=True: gs_prover_verify_device on this prover's backend context — the boundary values of registers with hundreds of
+        assertions and the long columns of public input registers come from the device; same answer, same message.  For an
         air-assembly component with input registers the trace length is not part of the job: the verifier reads the inputs' shapes
         from the proof, as the reference does (lib/Stark.ts:176), and lays the PUBLIC registers' values (publicInputs) out itself."""
+        job, _keep = self._verify_job(assertions, publicInputs)
+        err = C.create_string_buffer(512)
+        data = bytes(data)
+        if device:
+            rc = self.lib.gs_prover_verify_device_on(self.binding, self.backend.ctx, C.byref(job), data, len(data), err, 512)
+        else:
+            rc = self.lib.gs_prover_verify_on(self.binding, C.byref(job), data, len(data), err, 512)
+        if rc == -3:      # GS_ERR_UNSUPPORTED
+            raise GstarkError(err.value.decode(errors='replace') or 'unsupported by the native verifier')
+        if rc:
+            raise StarkError(err.value.decode(errors='replace') or f'verification failed ({rc})')
+        return True
+
+    def _verify_job(self, assertions, publicInputs=None):
+        """the statement as the verifier's gs_prover_job, and the objects its pointers refer to (keep them for as long as the job is used)"""
         air, f = self.stark.air, self.field
         if not isinstance(assertions, list) or len(assertions) == 0:
             raise TypeError('At least one assertion must be provided')
@@ -399,14 +420,18 @@ class NativeProver:
             ja.e_code, ja.e_ninstr, ja.consts, ja.nconsts, ja.vm_regs = e_code, e_n, consts, nconsts, nregs
             ja.static_values, ja.static_periods, ja.nstatic, ja.nsecret = pub, periods, len(plist), nsec
             keep += [e_code, consts, pub, periods]
-        err = C.create_string_buffer(512)
-        data = bytes(data)
-        rc = self.lib.gs_prover_verify_on(self.binding, C.byref(job), data, len(data), err, 512)
-        if rc == -3:      # GS_ERR_UNSUPPORTED
-            raise GstarkError(err.value.decode(errors='replace') or 'unsupported by the native verifier')
-        if rc:
-            raise StarkError(err.value.decode(errors='replace') or f'verification failed ({rc})')
-        return True
+        return job, keep
+
+    def verify(self, assertions, proof, publicInputs=None, device=False):
+        """verify_bytes for a proof given as bytes or as the parsed object (serialized again)."""
+        if not isinstance(proof, (bytes, bytearray, memoryview)):
+            proof = self.stark.serializer.serializeProof(proof) if hasattr(self.stark, 'serializer') else self.stark.serialize(proof)
+        return self.verify_bytes(assertions, bytes(proof), publicInputs, device=device)
+
+    def verify_device_min(self, assertions=0, column=0):
+        """The thresholds of verify_bytes(device=True) for the calling thread's next verifications (gs_prover_verify_device_min):
+        registers with more assertions / columns with a longer period than this go to the device; 0 = the default."""
+        self.lib.gs_prover_verify_device_min(int(assertions), int(column))
 
     def _pack_rows(self, rows):
         f = self.field

@@ -70,15 +70,19 @@ class Prover:
     def last_collectives(self):
         return self._native.last_collectives()
 
-    def verify_native(self, assertions, data, publicInputs=None):
+    def verify_native(self, assertions, data, publicInputs=None, device=False):
         """Stark.verify of serialized proof bytes by the NATIVE verifier (csrc/verifier.h; CPU only, ~100x the Python verifier's speed):
         True or StarkError with the reference's message.  publicInputs: the values of the public input registers of an air-assembly
         component (lib/Stark.ts:167); the trace is sized from the shapes the proof carries."""
-        return self._native.verify_bytes(assertions, data, publicInputs)
+        return self._native.verify_bytes(assertions, data, publicInputs, device=device)
 
-    def verify(self, assertions, proof, publicInputs=None):
+    def verify(self, assertions, proof, publicInputs=None, device=False):
         """lib/Stark.ts:167-248 on the CPU side of the same backend (the restated caller in genstark_amd/_mirror; a verifier that
-        needs no device at all is Stark(air over HostField(), options).verify, tests/test_host_verifier.py)."""
+        needs no device at all is Stark(air over HostField(), options).verify, tests/test_host_verifier.py).
+        device=True: the native verifier with the device's help for statements with hundreds of assertions per register or long public
+        input columns (gs_prover_verify_device on this prover's backend context): the same True, or StarkError with the same message."""
+        if device:
+            return self._native.verify(assertions, proof, publicInputs, device=True)
         from ._mirror.stark import Stark
         stark = Stark(self.air, self.options)
         if isinstance(proof, (bytes, bytearray, memoryview)):

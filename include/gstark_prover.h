@@ -161,6 +161,9 @@ int gs_prover_prove_on(const gs_prover_binding *b, gs_ctx *ctx, const struct gs_
  * length must be the ones the domain implies (fold while more than 256 values are left) — anything else is a malformed proof. */
 int gs_prover_verify(const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap);
 int gs_prover_verify_on(const gs_prover_binding *b, const struct gs_prover_job *job, const uint8_t *proof, uint64_t len, char *err, uint64_t errcap);
+/* gs_prover_verify_device / gs_prover_verify_device_on — the same verification with the device's help for the long polynomials of a
+ * statement (hundreds of assertions on a register, long public input columns) — are declared next to the optional entry points they
+ * use, in gstark_boundary.h. */
 int gs_prover_last_stats(struct gs_prover_stats *out);
 /* LowDegreeProver.verifyRemainder (LowDegreeProver.ts:223-252) on its own, for tests: `len` values on the powers of root_of_unity
  * (order len); 1 = the values at the positions that are not multiples of extension_factor lie on a polynomial of degree

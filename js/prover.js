@@ -82,9 +82,9 @@ function proveAssemblySerialized(assemblyAir, options, assertions, inputs, seed)
     job.inputShapes = [].concat(...context.inputShapes.map(sh => [sh.length].concat(sh)));
     return context.air.field.lib.proveGenericSerialized(context.air.field.ctx, driverPath(context.air.field), job);
 }
-function verifyAssemblySerialized(assemblyAir, options, assertions, proof, publicInputs) {
+function verifyAssemblySerialized(assemblyAir, options, assertions, proof, publicInputs, how) {
     if (!(options.hashAlgorithm in HASH_ALG)) throw new TypeError(`Hash algorithm ${options.hashAlgorithm} is not supported`);
-    if (!assemblyAir.info.inputRegisters) return verifyGenericSerialized(assemblyAir.generic, options, assertions, proof);
+    if (!assemblyAir.info.inputRegisters) return verifyGenericSerialized(assemblyAir.generic, options, assertions, proof, how);
     const f = assemblyAir.field, info = assemblyAir.info, e = info.evaluation;
     // the field's root of unity of the largest power-of-two order (at most 2^32): the driver squares it down to the evaluation domain's
     let adicity = 0;
@@ -105,12 +105,15 @@ function verifyAssemblySerialized(assemblyAir, options, assertions, proof, publi
         staticSources: [].concat(...info.staticSources), publicInputs: lists.length ? Buffer.concat(lists.map(l => f.packLe(l, v => f.mod(v)))) : Buffer.alloc(0),
         publicInputCounts: lists.map(l => l.length),
     };
-    return f.lib.proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
+    return f.lib.proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof), onDevice(how));
 }
 
 // Stark.verify() of serialized proof bytes by the NATIVE verifier (genstark_amd/csrc/verifier.h; CPU only, no device work): true, or throws
 // the reference's message.  The job carries what a verifier needs of the statement: no trace tables, no first rows.
-function verifyMimcSerialized(air, options, assertions, proof) {
+// A last argument {device: true} asks for the device-assisted verifier on the field's context (gs_prover_verify_device: registers with
+// hundreds of assertions, long public input columns): the same answer and message; the default stays host only.
+const onDevice = how => !!(how && how.device);
+function verifyMimcSerialized(air, options, assertions, proof, how) {
     const f = air.field, root = air._root !== undefined ? air._root : f.getRootOfUnity(air.steps * air.extensionFactor);
     const job = {
         steps: air.steps, extensionFactor: air.extensionFactor, exeQueryCount: options.exeQueryCount, friQueryCount: options.friQueryCount,
@@ -118,9 +121,9 @@ function verifyMimcSerialized(air, options, assertions, proof) {
         roundConstants: Buffer.concat(air.roundConstants.map(v => f.le(v))), kTable: 0n, kLen: 0,
         assertions: assertions.map(a => ({ step: a.step, register: a.register, value: f.le(f.mod(a.value)) })),
     };
-    return f.lib.proveMimcSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
+    return f.lib.proveMimcSerialized(f.ctx, driverPath(f), job, Buffer.from(proof), onDevice(how));
 }
-function verifyGenericSerialized(air, options, assertions, proof) {
+function verifyGenericSerialized(air, options, assertions, proof, how) {
     const f = air.field, e = air.evaluationProgram;
     const statics = [].concat(...air.staticRegisters);
     const job = {
@@ -133,7 +136,7 @@ function verifyGenericSerialized(air, options, assertions, proof) {
         staticTables: 0n, staticLens: air.staticRegisters.map(() => 0), firstRows: Buffer.alloc(air.traceRegisterCount * f.elementSize),
         segments: 0, segmentLen: 0,
     };
-    return f.lib.proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof));
+    return f.lib.proveGenericSerialized(f.ctx, driverPath(f), job, Buffer.from(proof), onDevice(how));
 }
 
 /** seed (as proveGenericSerialized takes it) -> the first rows packed once, for many proofs: what a caller whose inputs already are bytes

@@ -115,6 +115,7 @@ const FnDesc kFns[] = {
     {"gs_small_interpolate", "bbio"},
     // include/gstark_boundary.h: OPTIONAL on a library (symbols are resolved per call: a library without it answers "symbol not found")
     {"gs_boundary_polys", "cbuuxbwiipp"},
+    {"gs_eval_polys_at_points", "cpiuxbip"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
@@ -490,13 +491,20 @@ const Driver *open_driver(napi_env env, Lib *L, napi_value path_value) {
 }
 typedef int (*verify_on_fn)(const gs_prover_binding *, const gs_prover_job *, const uint8_t *, uint64_t, char *, uint64_t);
 // a 4th argument (a Buffer holding a serialized proof) turns either call below into Stark.verify() of that proof for the statement the job
-// describes (include/gstark_prover.h: gs_prover_verify_on — native, CPU only): returns true or throws the reference's message
-napi_value verify_instead(napi_env env, const Driver *drv, napi_value proof_value, const gs_prover_job &job) {
+// describes (include/gstark_prover.h: gs_prover_verify_on — native, CPU only): returns true or throws the reference's message.
+// A 5th argument `true` asks for gs_prover_verify_device_on with the member's context (the long polynomials of a statement on the device:
+// same answer, same message); a driver build without that entry verifies on the host.
+typedef int (*verify_device_on_fn)(const gs_prover_binding *, gs_ctx *, const gs_prover_job *, const uint8_t *, uint64_t, char *, uint64_t);
+napi_value verify_instead(napi_env env, const Driver *drv, napi_value proof_value, const gs_prover_job &job, void *ctx, napi_value device_value) {
     void *d;
     size_t len;
     if (!buffer_info(env, proof_value, &d, &len)) { napi_throw_type_error(env, nullptr, "the proof must be a Buffer"); return nullptr; }
+    bool device = false;
+    if (device_value && napi_get_value_bool(env, device_value, &device) != napi_ok) { napi_throw_type_error(env, nullptr, "device: a boolean expected"); return nullptr; }
     char err[512] = {0};
-    const int rc = ((verify_on_fn)dlsym(drv->dl, "gs_prover_verify_on"))(drv->binding, &job, (const uint8_t *)d, len, err, sizeof err);
+    verify_device_on_fn on_device = device ? (verify_device_on_fn)dlsym(drv->dl, "gs_prover_verify_device_on") : nullptr;
+    const int rc = on_device ? on_device(drv->binding, (gs_ctx *)ctx, &job, (const uint8_t *)d, len, err, sizeof err)
+                             : ((verify_on_fn)dlsym(drv->dl, "gs_prover_verify_on"))(drv->binding, &job, (const uint8_t *)d, len, err, sizeof err);
     if (rc != GS_OK) { napi_throw_error(env, nullptr, err[0] ? err : "verification failed"); return nullptr; }
     napi_value t;
     NAPI_OK(env, napi_get_boolean(env, true, &t));
@@ -518,8 +526,8 @@ const Driver *one_call_head(napi_env env, napi_callback_info info, size_t *argc,
     return open_driver(env, *L, argv[1]);
 }
 napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
+    size_t argc = 5;
+    napi_value argv[5];
     void *ctx = nullptr;
     Lib *L = nullptr;
     const Driver *drv = one_call_head(env, info, &argc, argv, &L, &ctx);
@@ -565,7 +573,7 @@ napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
         as[i].step = step; as[i].reg = (uint32_t)reg; memcpy(as[i].value, val, es);
     }
     job.assertions = as.data(); job.nassertions = na;
-    if (argc >= 4) return verify_instead(env, drv, argv[3], job);
+    if (argc >= 4) return verify_instead(env, drv, argv[3], job, ctx, argc >= 5 ? argv[4] : nullptr);
     static thread_local std::vector<uint8_t> out;      // (kept between calls: a fresh vector of this size is 4 MB of zeroing per proof)
     if (out.size() < (1u << 22)) out.resize(1u << 22);
     uint64_t n = 0;
@@ -583,8 +591,8 @@ napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
 //           tCode / iCode / eCode: number[] (4 words per instruction), consts: Buffer(16 * nconsts), vmRegs, staticValues: Buffer, staticPeriods: number[],
 //           staticTables: BigInt (device pointer), staticLens: number[], firstRows: Buffer, segments, segmentLen }
 napi_value ProveGenericSerialized(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
+    size_t argc = 5;
+    napi_value argv[5];
     void *ctx = nullptr;
     Lib *L = nullptr;
     const Driver *drv = one_call_head(env, info, &argc, argv, &L, &ctx);
@@ -719,7 +727,7 @@ napi_value ProveGenericSerialized(napi_env env, napi_callback_info info) {
         as[i].step = step; as[i].reg = (uint32_t)reg; memcpy(as[i].value, val, es);
     }
     job.assertions = as.data(); job.nassertions = na;
-    if (argc >= 4) return verify_instead(env, drv, argv[3], job);
+    if (argc >= 4) return verify_instead(env, drv, argv[3], job, ctx, argc >= 5 ? argv[4] : nullptr);
     static thread_local std::vector<uint8_t> out;      // (kept between calls: a fresh vector of this size is 4 MB of zeroing per proof)
     if (out.size() < (1u << 22)) out.resize(1u << 22);
     uint64_t n = 0;
