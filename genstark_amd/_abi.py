@@ -139,6 +139,18 @@ _OPTIONAL_SIGNATURES = {
 }
 OPTIONAL_SYMBOLS = tuple(_OPTIONAL_SIGNATURES)
 
+# include/gstark_hades.h: Poseidon hashes and Poseidon Merkle trees on the device; optional in the same way (genstark_amd/hades.py
+# computes on host integers where a library lacks them)
+_HADES_SIGNATURES = {
+    'gs_hades_create': (_int, [_vp, _u32, _u32, _u32, _u64, _bytes, _bytes, _pvp]),
+    'gs_hades_destroy': (_int, [_vp, _vp]),
+    'gs_hades_hash': (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _vp]),
+    'gs_hades_merkle': (_int, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    'gs_hades_merkle_paths': (_int, [_vp, _vp, _u64, _u32, C.POINTER(_u64), _u64, _vp]),
+    'gs_hades_merkle_top': (_u32, []),
+}
+HADES_SYMBOLS = tuple(_HADES_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -153,7 +165,7 @@ def load_library(path):
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in _OPTIONAL_SIGNATURES.items():
+    for name, (res, args) in list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

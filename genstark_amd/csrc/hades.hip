@@ -1,0 +1,276 @@
+// hades.hip — Hades permutations (Poseidon hashes) and Poseidon Merkle trees (include/gstark_hades.h; examples/poseidon/utils.ts:19-49,
+// 126-210 of the reference).  One thread runs one permutation with its state in registers; the width is a template argument (2 .. 8) so
+// that every index into the state is a constant — rounds, alpha and the constants are run-time values.
+//   constants   round constants ((rf + rp) x W) and the matrix (W x W) lie in ONE device block per parameter set (gs_hades_create) and
+//               are read through `const fe *__restrict__` at indexes that do not depend on the lane: the compiler turns those reads
+//               into scalar loads (through the scalar cache, into SGPRs), so the constants cost no VGPRs, no LDS and no barrier, and a
+//               product by one of them is a product by a wave-uniform operand.  (Up to 568 elements: too many for kernel arguments.)
+//   inputs      a workgroup's 256 rows of `arity` elements are one contiguous run of memory: it is copied into LDS with consecutive
+//               lanes on consecutive elements, then every thread picks its row up from there; the digests leave the same way.
+//   tree        node i = digest(permute(node 2i || node 2i + 1)), heap layout.  The inputs of ALL nodes of one level are the level
+//               below, contiguous, in rows of 2 * digest elements: a level IS a k_hades_hash launch (in = the level below, out = the
+//               level) — there is no second copy of the kernel.  The levels of at most GS_HADES_BLOCK nodes are one launch of one
+//               workgroup (k_hades_merkle_top): the level lives in LDS, a barrier separates the levels.  Nothing here synchronises
+//               between workgroups.
+#include "common.h"
+#include "../../include/gstark_hades.h"
+
+#define GS_HADES_BLOCK 256
+
+struct gs_hades {
+    gs_ctx *ctx;
+    uint32_t width, rf, rp;
+    uint64_t alpha;
+    fe *consts;              // device: (rf + rp) x width round constants, then width x width matrix rows
+};
+
+// s[FIRST .. W) to the power e (>= 1), the elements side by side (independent chains); the squarings and products fe_pow_u64 makes:
+// none by one at the start, none after the top bit — x^5 is three products.  e is the same in every lane: scalar branches.
+template <int W, int FIRST>
+__device__ __forceinline__ void hades_sbox(fe (&s)[W], uint64_t e) {
+    fe b[W];
+#pragma unroll
+    for (int j = FIRST; j < W; j++) b[j] = s[j];
+#pragma unroll 1
+    while (!(e & 1u)) {
+#pragma unroll
+        for (int j = FIRST; j < W; j++) b[j] = fe_mul(b[j], b[j]);
+        e >>= 1;
+    }
+#pragma unroll
+    for (int j = FIRST; j < W; j++) s[j] = b[j];
+#pragma unroll 1
+    for (e >>= 1; e; e >>= 1) {
+#pragma unroll
+        for (int j = FIRST; j < W; j++) b[j] = fe_mul(b[j], b[j]);
+        if (e & 1u) {
+#pragma unroll
+            for (int j = FIRST; j < W; j++) s[j] = fe_mul(s[j], b[j]);
+        }
+    }
+}
+
+template <int W>
+__device__ __forceinline__ void hades_permute(fe (&s)[W], const fe *__restrict__ consts, uint32_t rf, uint32_t rp, uint64_t alpha) {
+    const uint32_t half = rf / 2, rounds = rf + rp;
+    const fe *__restrict__ mds = consts + (uint64_t)rounds * W;
+#pragma unroll 1
+    for (uint32_t r = 0; r < rounds; r++) {
+        const fe *__restrict__ ark = consts + (uint64_t)r * W;
+#pragma unroll
+        for (int j = 0; j < W; j++) s[j] = fe_add(s[j], ark[j]);
+        if (r < half || r >= half + rp) hades_sbox<W, 0>(s, alpha);
+        else hades_sbox<W, W - 1>(s, alpha);
+        fe t[W];
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            fe acc = fe_mul(mds[i * W], s[0]);
+#pragma unroll
+            for (int j = 1; j < W; j++) acc = fe_add(acc, fe_mul(mds[i * W + j], s[j]));
+            t[i] = acc;
+        }
+#pragma unroll
+        for (int i = 0; i < W; i++) s[i] = t[i];
+    }
+}
+
+// `count` permutations of rows of `arity` elements (1 <= arity < W), `digest` (1 or 2) elements out each; one workgroup per 256 rows
+template <int W>
+__global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_hash(const fe *__restrict__ in, uint64_t count, uint32_t arity, uint32_t digest,
+                                                               const fe *__restrict__ consts, uint32_t rf, uint32_t rp, uint64_t alpha, fe *__restrict__ out) {
+    __shared__ fe stage[GS_HADES_BLOCK * (W - 1 > 2 ? W - 1 : 2)];          // rows x arity in, then rows x digest out
+    const uint32_t t = threadIdx.x;
+    const uint64_t first = (uint64_t)blockIdx.x * GS_HADES_BLOCK;
+    const uint32_t rows = count - first < GS_HADES_BLOCK ? (uint32_t)(count - first) : GS_HADES_BLOCK;
+    const fe *__restrict__ src = in + first * arity;
+    for (uint32_t k = t; k < rows * arity; k += GS_HADES_BLOCK) stage[k] = src[k];
+    __syncthreads();
+    fe s[W];
+    if (t < rows) {
+#pragma unroll
+        for (int j = 0; j < W; j++) s[j] = j < (int)arity ? stage[t * arity + j] : fe_zero();
+        hades_permute<W>(s, consts, rf, rp, alpha);
+    }
+    __syncthreads();                                                         // every row has been picked up: the stage takes the digests
+    if (t < rows) {
+        stage[t * digest] = s[0];
+        if (digest > 1) stage[t * digest + 1] = s[1];
+    }
+    __syncthreads();
+    fe *__restrict__ dst = out + first * digest;
+    for (uint32_t k = t; k < rows * digest; k += GS_HADES_BLOCK) dst[k] = stage[k];
+}
+
+// the top of a tree in one workgroup: reads nodes 2m .. 4m - 1 (m a power of two <= GS_HADES_BLOCK: the widest level computed here),
+// writes nodes 1 .. 2m - 1 and the zero of node 0.  The level just computed stays in LDS for the next one.
+template <int W>
+__global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_merkle_top(fe *nodes,uint32_t m, uint32_t digest, const fe *__restrict__ consts,
+                                                                     uint32_t rf, uint32_t rp, uint64_t alpha) {
+    __shared__ fe level[2 * GS_HADES_BLOCK * 2];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t k = t; k < 2 * m * digest; k += GS_HADES_BLOCK) level[k] = nodes[2 * m * digest + k];
+    if (t < digest) nodes[t] = fe_zero();
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t cnt = m; cnt >= 1; cnt >>= 1) {
+        fe s[W];
+        if (t < cnt) {
+#pragma unroll
+            for (int j = 0; j < W; j++) s[j] = j < 4 && j < (int)(2 * digest) ? level[t * 2 * digest + j] : fe_zero();
+            hades_permute<W>(s, consts, rf, rp, alpha);
+        }
+        __syncthreads();                                                     // the level below has been read by everyone
+        if (t < cnt) {
+            level[t * digest] = s[0];
+            nodes[(cnt + t) * digest] = s[0];
+            if (digest > 1) { level[t * digest + 1] = s[1]; nodes[(cnt + t) * digest + 1] = s[1]; }
+        }
+        __syncthreads();
+    }
+}
+
+// out[path][level][e]: the leaf (level 0), then the sibling on every level from the leaves up
+__global__ __launch_bounds__(256) void k_hades_paths(const fe *__restrict__ nodes, uint64_t n, uint32_t depth, uint32_t digest, const uint64_t *__restrict__ idx,
+                                                     uint64_t total, fe *__restrict__ out) {
+    const uint64_t per_path = (uint64_t)(depth + 1) * digest;
+    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t path = t / per_path, e = t % digest;
+        const uint32_t l = (uint32_t)((t % per_path) / digest);
+        const uint64_t leaf = n + idx[path];
+        const uint64_t node = l ? ((leaf >> (l - 1)) ^ 1) : leaf;
+        out[t] = nodes[node * digest + e];
+    }
+}
+
+namespace {
+
+#define GS_HADES_WIDTHS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+
+int launch_hash(gs_ctx *c, const gs_hades *h, const fe *in, uint64_t count, uint32_t arity, uint32_t digest, fe *out) {
+    const uint64_t blocks = (count + GS_HADES_BLOCK - 1) / GS_HADES_BLOCK;
+    switch (h->width) {
+#define X(W)                                                                                                                                         \
+    case W:                                                                                                                                          \
+        hipLaunchKernelGGL(k_hades_hash<W>, dim3((unsigned)blocks), dim3(GS_HADES_BLOCK), 0, c->stream, in, count, arity, digest, (const fe *)h->consts, \
+                           h->rf, h->rp, h->alpha, out);                                                                                             \
+        break;
+        GS_HADES_WIDTHS(X)
+#undef X
+    }
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
+
+int launch_top(gs_ctx *c, const gs_hades *h, fe *nodes, uint32_t m, uint32_t digest) {
+    switch (h->width) {
+#define X(W)                                                                                                                                             \
+    case W:                                                                                                                                              \
+        hipLaunchKernelGGL(k_hades_merkle_top<(W < 3 ? 3 : W)>, dim3(1), dim3(GS_HADES_BLOCK), 0, c->stream, nodes, m, digest, (const fe *)h->consts, h->rf, \
+                           h->rp, h->alpha);                                                                                                             \
+        break;
+        GS_HADES_WIDTHS(X)                                                   // (a tree needs 2 * digest < width: width 2 never gets here)
+#undef X
+    }
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
+
+// products of one permutation: the S-boxes of rf full and rp partial rounds and the matrix of every round
+uint64_t hades_products(const gs_hades *h) {
+    uint64_t per_pow = 0;
+    for (uint64_t e = h->alpha; e > 1; e >>= 1) per_pow += 1 + (e & 1u);
+    const uint64_t w = h->width;
+    return h->rf * (w * per_pow + w * w) + h->rp * (per_pow + w * w);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t gs_hades_merkle_top(void) { return GS_HADES_BLOCK; }
+
+int gs_hades_create(gs_ctx *c, uint32_t width, uint32_t rf, uint32_t rp, uint64_t alpha, const uint8_t *rc_host, const uint8_t *mds_host, gs_hades **out) {
+    if (!c || !out) return GS_ERR_ARG;
+    *out = nullptr;
+    if (!rc_host || !mds_host) return gs_fail(c, GS_ERR_ARG, "hades_create: round constants and matrix are required");
+    if (width < 2 || width > 8) return gs_fail(c, GS_ERR_ARG, "hades_create: width %u is outside 2 .. 8", width);
+    if (rf < 2 || (rf & 1u) || rf > (1u << 16) || rp > (1u << 16))
+        return gs_fail(c, GS_ERR_ARG, "hades_create: %u full rounds (even, 2 .. 65536) and %u partial rounds (at most 65536)", rf, rp);
+    if (alpha < 2) return gs_fail(c, GS_ERR_ARG, "hades_create: alpha is at least 2");
+    const uint64_t nrc = (uint64_t)(rf + rp) * width, nmds = (uint64_t)width * width;
+    void *p = nullptr;
+    int rc = gs_alloc(c, (nrc + nmds) * GS_ELT, &p);
+    if (rc) return rc;
+    if ((rc = gs_push(c, p, rc_host, nrc * GS_ELT)) || (rc = gs_push(c, (fe *)p + nrc, mds_host, nmds * GS_ELT))) {
+        gs_free(c, p);
+        return rc;
+    }
+    *out = new gs_hades{c, width, rf, rp, alpha, (fe *)p};
+    return GS_OK;
+}
+
+int gs_hades_destroy(gs_ctx *c, gs_hades *h) {
+    if (!c) return GS_ERR_ARG;
+    if (!h) return GS_OK;
+    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "hades_destroy: the handle belongs to another context");
+    gs_free(c, h->consts);                                                   // parked in the context's cache: launches already queued still read it in order
+    delete h;
+    return GS_OK;
+}
+
+int gs_hades_hash(gs_ctx *c, const gs_hades *h, const void *in, uint64_t count, uint32_t arity, uint32_t digest, void *out) {
+    if (!c || !h) return GS_ERR_ARG;
+    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "hades_hash: the handle belongs to another context");
+    if (arity < 1 || arity >= h->width) return gs_fail(c, GS_ERR_ARG, "hades_hash: %u inputs do not fit a state of %u (1 .. %u)", arity, h->width, h->width - 1);
+    if (digest < 1 || digest > 2) return gs_fail(c, GS_ERR_ARG, "hades_hash: a digest of 1 or 2 elements, not %u", digest);
+    if (count > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "hades_hash: at most 2^36 permutations per call");
+    if (!count) return GS_OK;
+    if (!in || !out) return GS_ERR_ARG;
+    gs_traffic(c, count * (arity + digest) * GS_ELT, count * hades_products(h), "k_hades_hash<%u>", h->width);
+    return launch_hash(c, h, (const fe *)in, count, arity, digest, (fe *)out);
+}
+
+int gs_hades_merkle(gs_ctx *c, const gs_hades *h, const void *leaves, uint64_t n, uint32_t digest, void *nodes_out) {
+    if (!c || !h) return GS_ERR_ARG;
+    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "hades_merkle: the handle belongs to another context");
+    if (n < 2 || !gs_is_pow2(n) || n > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "hades_merkle: the number of leaves is a power of two, 2 .. 2^36");
+    if (digest < 1 || digest > 2 || 2 * digest >= h->width)
+        return gs_fail(c, GS_ERR_ARG, "hades_merkle: nodes of %u elements (1 or 2): two of them do not fit a state of %u beside its capacity", digest, h->width);
+    if (!leaves || !nodes_out) return GS_ERR_ARG;
+    fe *nodes = (fe *)nodes_out;
+    if (leaves != (const void *)(nodes + n * digest))
+        GS_HIP(c, hipMemcpyAsync(nodes + n * digest, leaves, n * digest * GS_ELT, hipMemcpyDeviceToDevice, c->stream));
+    uint64_t cnt = n / 2;
+    for (; cnt > GS_HADES_BLOCK; cnt /= 2) {                                 // wide levels: the level below is the input matrix of a hash launch
+        gs_traffic(c, 3 * cnt * digest * GS_ELT, cnt * hades_products(h), "k_hades_merkle_level<%u>", h->width);
+        const int rc = launch_hash(c, h, nodes + 2 * cnt * digest, cnt, 2 * digest, digest, nodes + cnt * digest);
+        if (rc) return rc;
+    }
+    gs_traffic(c, (4 * cnt - 1) * digest * GS_ELT, (2 * cnt - 1) * hades_products(h), "k_hades_merkle_top<%u>", h->width);
+    return launch_top(c, h, nodes, (uint32_t)cnt, digest);
+}
+
+int gs_hades_merkle_paths(gs_ctx *c, const void *nodes, uint64_t n, uint32_t digest, const uint64_t *indexes_host, uint64_t count, void *out) {
+    if (!c) return GS_ERR_ARG;
+    if (n < 2 || !gs_is_pow2(n) || n > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "hades_merkle_paths: the number of leaves is a power of two, 2 .. 2^36");
+    if (digest < 1 || digest > 2) return gs_fail(c, GS_ERR_ARG, "hades_merkle_paths: nodes of 1 or 2 elements, not %u", digest);
+    if (count > (1ull << 24)) return gs_fail(c, GS_ERR_ARG, "hades_merkle_paths: at most 2^24 paths per call");
+    if (!count) return GS_OK;
+    if (!nodes || !indexes_host || !out) return GS_ERR_ARG;
+    for (uint64_t k = 0; k < count; k++)
+        if (indexes_host[k] >= n)
+            return gs_fail(c, GS_ERR_ARG, "hades_merkle_paths: index %llu is outside of the %llu leaves", (unsigned long long)indexes_host[k], (unsigned long long)n);
+    const uint32_t depth = (uint32_t)gs_log2(n);
+    const uint64_t total = count * (depth + 1) * digest;
+    void *d_idx = nullptr;
+    int rc = gs_tmp_alloc(c, count * 8, &d_idx);
+    if (rc) return rc;
+    if ((rc = gs_push(c, d_idx, indexes_host, count * 8)) == GS_OK) {
+        hipLaunchKernelGGL(k_hades_paths, dim3(gs_grid(total)), dim3(256), 0, c->stream, (const fe *)nodes, n, depth, digest, (const uint64_t *)d_idx, total, (fe *)out);
+        if (hipGetLastError() != hipSuccess) rc = gs_fail(c, GS_ERR_DEVICE, "hades_merkle_paths: launch failed");
+    }
+    gs_tmp_free(c, d_idx);                                                   // (stream-ordered cache: the launch above still reads it)
+    return rc;
+}
+
+}  // extern "C"

@@ -203,3 +203,12 @@ class PoseidonMerkleTree:
             proof.append(self.nodes[index ^ 1])
             index >>= 1
         return proof
+
+
+def poseidon_tree(field, leaves):
+    """The same tree built on the device (genstark_amd/hades.py: HadesMerkleTree over lib128's matrix and `prng` round constants):
+    leaves as above, or a device Matrix of n x 2.  `root`, `prove(index)` and `nodes` are PoseidonMerkleTree's."""
+    from .hades import HadesHash, HadesMerkleTree
+    cols = round_constant_columns(field)
+    rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
+    return HadesMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, STATE_WIDTH, rc, MDS), leaves, 2)

@@ -182,6 +182,15 @@ class PoseidonMerkleTree:
         return proof
 
 
+def poseidon_tree(field, leaves):
+    """The same tree built on the device (genstark_amd/hades.py: HadesMerkleTree over lib224's matrix and `prng` round constants):
+    leaves as above, or a device Vector of n elements.  `root`, `prove(index)` and `nodes` are PoseidonMerkleTree's."""
+    from .hades import HadesHash, HadesMerkleTree
+    cols = round_constant_columns(field)
+    rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
+    return HadesMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, WIDTH, rc, MDS), leaves, 1)
+
+
 # ---- Schnorr signature verification ---------------------------------------------------------------------------------------------
 SCHNORR_DEGREES = [3, 4, 5, 6, 3, 4, 3, 3, 4, 4, 5, 3, 3, 3, 2, 2, 2, 2]
 

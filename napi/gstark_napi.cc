@@ -116,6 +116,13 @@ const FnDesc kFns[] = {
     // include/gstark_boundary.h: OPTIONAL on a library (symbols are resolved per call: a library without it answers "symbol not found")
     {"gs_boundary_polys", "cbuuxbwiipp"},
     {"gs_eval_polys_at_points", "cpiuxbip"},
+    // include/gstark_hades.h: OPTIONAL in the same way.  gs_hades_create writes the handle (a pointer) into an 8-byte Buffer; the handle
+    // then travels as a BigInt like a device pointer
+    {"gs_hades_create", "ciiiubbo"},
+    {"gs_hades_destroy", "cp"},
+    {"gs_hades_hash", "cppuiip"},
+    {"gs_hades_merkle", "cppuip"},
+    {"gs_hades_merkle_paths", "cpuixup"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
