@@ -151,6 +151,17 @@ _HADES_SIGNATURES = {
 }
 HADES_SYMBOLS = tuple(_HADES_SIGNATURES)
 
+# include/gstark_rescue.h: Rescue hashes and Rescue Merkle trees on the device; optional in the same way (genstark_amd/rescue_hash.py
+# computes on host integers where a library lacks them)
+_RESCUE_SIGNATURES = {
+    'gs_rescue_create': (_int, [_vp, _u32, _u32, _u64, _bytes, _bytes, _bytes, _pvp]),
+    'gs_rescue_destroy': (_int, [_vp, _vp]),
+    'gs_rescue_hash': (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _vp]),
+    'gs_rescue_merkle': (_int, [_vp, _vp, _vp, _u64, _vp]),
+    'gs_rescue_spread_limit': (_u64, []),
+}
+RESCUE_SYMBOLS = tuple(_RESCUE_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -165,7 +176,7 @@ def load_library(path):
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()):
+    for name, (res, args) in list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -1,0 +1,156 @@
+'use strict';
+// js/rescue.js — the Rescue helpers of the reference's examples/rescue/utils.ts with the bulk work on the device
+// (include/gstark_rescue.h through the addon's table): createRescue(field, alpha, invAlpha, registers, rounds, mds, constants) has the
+// members of the example's Rescue class (unrollConstants, groupConstants, sponge, modifiedSponge: BigInt arithmetic on the host, as
+// upstream) and .hash2(v1, v2) = makeHashFunction, plus .hashMany(matrix, digest, modified, form) — one permutation per row in one
+// launch — and .merkleTree(values): the example's MerkleTree (nodes, root, prove, static verify) built by the device, with
+// proveMany(indexes) in one read-back.  `field` is a PrimeField of js/galois.js.  A field whose library lacks the entry points (they
+// are optional on an implementation of the ABI) makes the device members throw an Error saying so.
+const { Matrix, Vector } = require('./galois.js');
+
+const registry = (typeof FinalizationRegistry !== 'undefined')
+    ? new FinalizationRegistry(({ lib, ctx, handle }) => { try { lib.call('gs_rescue_destroy', ctx, handle); } catch (e) { /* context gone */ } })
+    : null;
+
+function needDevice(field) {
+    if (!field.lib.has || !field.lib.has('gs_rescue_hash')) {
+        throw new Error(`the library of the field of ${field.modulus} elements has no gs_rescue_* entry points (include/gstark_rescue.h): Rescue hashes and trees are not computed on this device library`);
+    }
+}
+
+/** new Rescue(...) of utils.ts:33; invAlpha may be negative, as in the examples */
+function createRescue(field, alpha, invAlpha, registers, rounds, mds, constants) {
+    const m = registers, p = field.modulus;
+    alpha = BigInt(alpha); invAlpha = BigInt(invAlpha);
+    if (!(m >= 2 && m <= 8)) throw new Error(`createRescue: a state of ${m} elements is outside 2 .. 8`);
+    if (!(rounds >= 1)) throw new Error(`createRescue: ${rounds} rounds (at least 1)`);
+    if (alpha < 2n || alpha >> 64n) throw new Error(`createRescue: alpha ${alpha} is outside 2 .. 2^64 - 1`);
+    const invExponent = invAlpha > 0n ? invAlpha : p - 1n + invAlpha;          // (1/x)^|invAlpha| for every x, 0 -> 0
+    if (invExponent < 1n || invExponent >= p - 1n) throw new Error('createRescue: the inverse exponent is outside 1 .. p - 2');
+    const matrix = mds.map(row => row.map(v => field.mod(BigInt(v)))), c = constants.map(v => field.mod(BigInt(v)));
+    if (matrix.length !== m || matrix.some(row => row.length !== m)) throw new Error(`createRescue: the matrix has ${m} rows of ${m} values`);
+    if (c.length !== m * (m + 2)) throw new Error(`createRescue: ${m * (m + 2)} key constants are needed`);
+    const iConstants = c.slice(0, m), cConstants = c.slice(m + m * m), cMatrix = [];
+    for (let i = 0; i < m; i++) cMatrix.push(c.slice(m + i * m, m + (i + 1) * m));
+    const vadd = (a, b) => a.map((x, i) => (x + b[i]) % p);
+    const mmul = (a, v) => a.map(row => row.reduce((acc, x, j) => (acc + x * v[j]) % p, 0n));
+    const half = (state, e, key) => vadd(mmul(matrix, state.map(x => field.exp(x, e))), key);
+    const padded = inputs => {
+        if (!(inputs.length > 0 && inputs.length <= m)) throw new Error(`${inputs.length} inputs do not fit a state of ${m}`);
+        const state = inputs.map(v => field.mod(BigInt(v)));
+        while (state.length < m) state.push(0n);
+        return state;
+    };
+    let keys = null, handle = null;
+
+    const rescue = {
+        field, alpha, invAlpha, invExponent, registers: m, rounds, mds: matrix,
+        unrollConstants() {      // utils.ts:128-159
+            let state = iConstants.slice(), injection = iConstants;
+            const result = [state.slice()];
+            for (let r = 0; r <= rounds; r++) {
+                for (const e of [invExponent, alpha]) {
+                    injection = vadd(mmul(cMatrix, injection), cConstants);
+                    state = half(state, e, injection);
+                    result.push(state.slice());
+                }
+            }
+            return result;
+        },
+        get keys() { if (keys === null) keys = rescue.unrollConstants(); return keys; },
+        groupConstants(k = rescue.keys) {      // utils.ts:161-180
+            const roundConstants = [];
+            for (let j = 0; j < 2 * m; j++) roundConstants.push(new Array(rounds));
+            for (let i = 0; i < rounds; i++) {
+                for (let j = 0; j < m; j++) { roundConstants[j][i] = k[2 + 2 * i][j]; roundConstants[m + j][i] = k[3 + 2 * i][j]; }
+            }
+            return { initialConstants: [...k[0], ...k[1]], roundConstants };
+        },
+        sponge(inputs, k = rescue.keys) {      // utils.ts:49-88
+            let state = padded(inputs);
+            const trace = [state.slice()];
+            state = vadd(state, k[0]);
+            trace.push(state.slice());
+            for (let r = 0; r < rounds; r++) {
+                state = half(state, invExponent, k[2 * r + 1]); trace.push(state.slice());
+                state = half(state, alpha, k[2 * r + 2]); trace.push(state.slice());
+            }
+            return { hash: state.slice(0, inputs.length), trace };
+        },
+        modifiedSponge(inputs, k = rescue.keys) {      // utils.ts:90-124
+            let state = padded(inputs);
+            const trace = [state.slice()];
+            for (let r = 0; r < rounds - 1; r++) {
+                state = half(state, alpha, k[2 * r + 2]); trace.push(state.slice());
+                state = half(state, invExponent, k[2 * r + 3]); trace.push(state.slice());
+            }
+            return { hash: state.slice(0, inputs.length), trace };
+        },
+        /** makeHashFunction (utils.ts:11-15) */
+        hash2(v1, v2) {
+            const inputs = [v1, v2];
+            while (inputs.length < m) inputs.push(0n);
+            return rescue.modifiedSponge(inputs).hash[0];
+        },
+        /** the gs_rescue of this parameter set on the field's context (a BigInt): constants uploaded once, on first use */
+        handle() {
+            if (handle === null) {
+                needDevice(field);
+                const out = Buffer.alloc(8);
+                field.lib.call('gs_rescue_create', field.ctx, m, rounds, alpha, field.packLe([invExponent]), field.packLe([].concat(...matrix)),
+                    field.packLe([].concat(...rescue.keys)), out);
+                handle = out.readBigUInt64LE(0);
+                if (registry) registry.register(rescue, { lib: field.lib, ctx: field.ctx, handle });
+            }
+            return handle;
+        },
+        /** one permutation per row of a device Matrix (or of rows of BigInts): a Matrix of rowCount x digest */
+        hashMany(rows, digest = 1, modified = true, form = 0) {
+            needDevice(field);
+            if (!(rows instanceof Matrix)) rows = field.newMatrixFrom(rows);
+            field._own(rows);
+            const out = new Matrix(field, rows.rowCount, digest);
+            field.lib.call('gs_rescue_hash', field.ctx, rescue.handle(), rows.ptr, rows.rowCount, rows.colCount, digest, modified ? 1 : 0, form, out.ptr);
+            return out;
+        },
+        merkleTree(values) { return new MerkleTree(values, rescue); },
+    };
+    return rescue;
+}
+
+class MerkleTree {      // utils.ts:232-273, built by the device
+    constructor(values, rescue) {
+        const field = rescue.field;
+        if (!field || !rescue.handle) throw new Error('the hash must come from createRescue of js/rescue.js');
+        needDevice(field);
+        const src = Array.isArray(values) ? field.newVectorFrom(values) : values;
+        if (!(src instanceof Vector)) throw new Error('the leaves are an array of BigInts or a Vector');
+        field._own(src);
+        const n = src.length;
+        this.field = field; this.rescue = rescue; this.leafCount = n;
+        this.depth = Math.round(Math.log2(n));
+        this.deviceNodes = new Vector(field, 2 * n);
+        field.lib.call('gs_rescue_merkle', field.ctx, rescue.handle(), src.ptr, n, this.deviceNodes.ptr);
+    }
+    get nodes() { const values = this.deviceNodes.toValues(); values[0] = undefined; return values; }
+    get root() { return this.deviceNodes.getValue(1); }
+    prove(index) { return this.proveMany([index])[0]; }
+    /** prove(index) for every index (repeats allowed): one launch, one read-back */
+    proveMany(indexes) {
+        if (!indexes.length) return [];
+        const per = this.depth + 1, out = new Vector(this.field, indexes.length * per);
+        this.field.lib.call('gs_hades_merkle_paths', this.field.ctx, this.deviceNodes.ptr, this.leafCount, 1, indexes, indexes.length, out.ptr);
+        const values = out.toValues();
+        return indexes.map((_, k) => values.slice(k * per, (k + 1) * per));
+    }
+    /** hash: a function of two values (rescue.hash2) */
+    static verify(root, index, proof, hash) {
+        let v = proof[0];
+        for (let level = 1; level < proof.length; level++) {
+            v = Math.floor(index / 2 ** (level - 1)) % 2 === 1 ? hash(proof[level], v) : hash(v, proof[level]);
+        }
+        return root === v;
+    }
+}
+
+module.exports = { createRescue, MerkleTree };

@@ -123,6 +123,11 @@ const FnDesc kFns[] = {
     {"gs_hades_hash", "cppuiip"},
     {"gs_hades_merkle", "cppuip"},
     {"gs_hades_merkle_paths", "cpuixup"},
+    // include/gstark_rescue.h: OPTIONAL in the same way; the handle travels like gs_hades_create's.  Paths: gs_hades_merkle_paths
+    {"gs_rescue_create", "ciiubbbo"},
+    {"gs_rescue_destroy", "cp"},
+    {"gs_rescue_hash", "cppuiiiip"},
+    {"gs_rescue_merkle", "cppup"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
