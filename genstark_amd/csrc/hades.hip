@@ -5,14 +5,13 @@
 //               are read through `const fe *__restrict__` at indexes that do not depend on the lane: the compiler turns those reads
 //               into scalar loads (through the scalar cache, into SGPRs), so the constants cost no VGPRs, no LDS and no barrier, and a
 //               product by one of them is a product by a wave-uniform operand.  (Up to 568 elements: too many for kernel arguments.)
-//   inputs      a workgroup's 256 rows of `arity` elements are one contiguous run of memory: it is copied into LDS with consecutive
-//               lanes on consecutive elements, then every thread picks its row up from there; the digests leave the same way.
-//   tree        node i = digest(permute(node 2i || node 2i + 1)), heap layout.  The inputs of ALL nodes of one level are the level
-//               below, contiguous, in rows of 2 * digest elements: a level IS a k_hades_hash launch (in = the level below, out = the
-//               level) — there is no second copy of the kernel.  The levels of at most GS_HADES_BLOCK nodes are one launch of one
-//               workgroup (k_hades_merkle_top): the level lives in LDS, a barrier separates the levels.  Nothing here synchronises
-//               between workgroups.
-#include "common.h"
+//   inputs      a workgroup's 256 rows pass through LDS both ways: the staged row kernel body of sponge_common.h.
+//   tree        node i = digest(permute(node 2i || node 2i + 1)), heap layout.  A wide level IS a k_hades_hash launch over the level
+//               below (the level loop of sponge_common.h) — there is no second copy of the kernel.  The levels of at most
+//               GS_HADES_BLOCK nodes are one launch of one workgroup (k_hades_merkle_top): the level lives in LDS, a barrier
+//               separates the levels.  Nothing here synchronises between workgroups.
+//   paths       k_hades_paths / gs_hades_merkle_paths read nothing but a node array: family-neutral (sponge_common.h), defined here.
+#include "sponge_common.h"
 #include "../../include/gstark_hades.h"
 
 #define GS_HADES_BLOCK 256
@@ -78,27 +77,7 @@ __device__ __forceinline__ void hades_permute(fe (&s)[W], const fe *__restrict__
 template <int W>
 __global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_hash(const fe *__restrict__ in, uint64_t count, uint32_t arity, uint32_t digest,
                                                                const fe *__restrict__ consts, uint32_t rf, uint32_t rp, uint64_t alpha, fe *__restrict__ out) {
-    __shared__ fe stage[GS_HADES_BLOCK * (W - 1 > 2 ? W - 1 : 2)];          // rows x arity in, then rows x digest out
-    const uint32_t t = threadIdx.x;
-    const uint64_t first = (uint64_t)blockIdx.x * GS_HADES_BLOCK;
-    const uint32_t rows = count - first < GS_HADES_BLOCK ? (uint32_t)(count - first) : GS_HADES_BLOCK;
-    const fe *__restrict__ src = in + first * arity;
-    for (uint32_t k = t; k < rows * arity; k += GS_HADES_BLOCK) stage[k] = src[k];
-    __syncthreads();
-    fe s[W];
-    if (t < rows) {
-#pragma unroll
-        for (int j = 0; j < W; j++) s[j] = j < (int)arity ? stage[t * arity + j] : fe_zero();
-        hades_permute<W>(s, consts, rf, rp, alpha);
-    }
-    __syncthreads();                                                         // every row has been picked up: the stage takes the digests
-    if (t < rows) {
-        stage[t * digest] = s[0];
-        if (digest > 1) stage[t * digest + 1] = s[1];
-    }
-    __syncthreads();
-    fe *__restrict__ dst = out + first * digest;
-    for (uint32_t k = t; k < rows * digest; k += GS_HADES_BLOCK) dst[k] = stage[k];
+    GS_SPONGE_HASH_ROWS(GS_HADES_BLOCK, W, W - 1 > 2 ? W - 1 : 2, hades_permute<W>(s, consts, rf, rp, alpha));
 }
 
 // the top of a tree in one workgroup: reads nodes 2m .. 4m - 1 (m a power of two <= GS_HADES_BLOCK: the widest level computed here),
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_merkle_top(fe *nodes,u
     }
 }
 
-// out[path][level][e]: the leaf (level 0), then the sibling on every level from the leaves up
+// out[path][level][e]: the leaf (level 0), then the sibling on every level from the leaves up — of any tree in the heap layout
 __global__ __launch_bounds__(256) void k_hades_paths(const fe *__restrict__ nodes, uint64_t n, uint32_t depth, uint32_t digest, const uint64_t *__restrict__ idx,
                                                      uint64_t total, fe *__restrict__ out) {
     const uint64_t per_path = (uint64_t)(depth + 1) * digest;
@@ -144,8 +123,6 @@ __global__ __launch_bounds__(256) void k_hades_paths(const fe *__restrict__ node
 
 namespace {
 
-#define GS_HADES_WIDTHS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-
 int launch_hash(gs_ctx *c, const gs_hades *h, const fe *in, uint64_t count, uint32_t arity, uint32_t digest, fe *out) {
     const uint64_t blocks = (count + GS_HADES_BLOCK - 1) / GS_HADES_BLOCK;
     switch (h->width) {
@@ -154,7 +131,7 @@ int launch_hash(gs_ctx *c, const gs_hades *h, const fe *in, uint64_t count, uint
         hipLaunchKernelGGL(k_hades_hash<W>, dim3((unsigned)blocks), dim3(GS_HADES_BLOCK), 0, c->stream, in, count, arity, digest, (const fe *)h->consts, \
                            h->rf, h->rp, h->alpha, out);                                                                                             \
         break;
-        GS_HADES_WIDTHS(X)
+        GS_SPONGE_WIDTHS(X)
 #undef X
     }
     GS_LAUNCH_CHECK(c);
@@ -168,7 +145,7 @@ int launch_top(gs_ctx *c, const gs_hades *h, fe *nodes, uint32_t m, uint32_t dig
         hipLaunchKernelGGL(k_hades_merkle_top<(W < 3 ? 3 : W)>, dim3(1), dim3(GS_HADES_BLOCK), 0, c->stream, nodes, m, digest, (const fe *)h->consts, h->rf, \
                            h->rp, h->alpha);                                                                                                             \
         break;
-        GS_HADES_WIDTHS(X)                                                   // (a tree needs 2 * digest < width: width 2 never gets here)
+        GS_SPONGE_WIDTHS(X)                                                   // (a tree needs 2 * digest < width: width 2 never gets here)
 #undef X
     }
     GS_LAUNCH_CHECK(c);
@@ -177,9 +154,7 @@ int launch_top(gs_ctx *c, const gs_hades *h, fe *nodes, uint32_t m, uint32_t dig
 
 // products of one permutation: the S-boxes of rf full and rp partial rounds and the matrix of every round
 uint64_t hades_products(const gs_hades *h) {
-    uint64_t per_pow = 0;
-    for (uint64_t e = h->alpha; e > 1; e >>= 1) per_pow += 1 + (e & 1u);
-    const uint64_t w = h->width;
+    const uint64_t w = h->width, per_pow = sponge_pow_products(h->alpha);
     return h->rf * (w * per_pow + w * w) + h->rp * (per_pow + w * w);
 }
 
@@ -199,31 +174,19 @@ int gs_hades_create(gs_ctx *c, uint32_t width, uint32_t rf, uint32_t rp, uint64_
     if (alpha < 2) return gs_fail(c, GS_ERR_ARG, "hades_create: alpha is at least 2");
     const uint64_t nrc = (uint64_t)(rf + rp) * width, nmds = (uint64_t)width * width;
     void *p = nullptr;
-    int rc = gs_alloc(c, (nrc + nmds) * GS_ELT, &p);
+    const int rc = sponge_upload(c, {{rc_host, nrc * GS_ELT}, {mds_host, nmds * GS_ELT}}, &p);
     if (rc) return rc;
-    if ((rc = gs_push(c, p, rc_host, nrc * GS_ELT)) || (rc = gs_push(c, (fe *)p + nrc, mds_host, nmds * GS_ELT))) {
-        gs_free(c, p);
-        return rc;
-    }
     *out = new gs_hades{c, width, rf, rp, alpha, (fe *)p};
     return GS_OK;
 }
 
-int gs_hades_destroy(gs_ctx *c, gs_hades *h) {
-    if (!c) return GS_ERR_ARG;
-    if (!h) return GS_OK;
-    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "hades_destroy: the handle belongs to another context");
-    gs_free(c, h->consts);                                                   // parked in the context's cache: launches already queued still read it in order
-    delete h;
-    return GS_OK;
-}
+int gs_hades_destroy(gs_ctx *c, gs_hades *h) { return sponge_destroy(c, h, "hades_destroy"); }
 
 int gs_hades_hash(gs_ctx *c, const gs_hades *h, const void *in, uint64_t count, uint32_t arity, uint32_t digest, void *out) {
-    if (!c || !h) return GS_ERR_ARG;
-    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "hades_hash: the handle belongs to another context");
-    if (arity < 1 || arity >= h->width) return gs_fail(c, GS_ERR_ARG, "hades_hash: %u inputs do not fit a state of %u (1 .. %u)", arity, h->width, h->width - 1);
-    if (digest < 1 || digest > 2) return gs_fail(c, GS_ERR_ARG, "hades_hash: a digest of 1 or 2 elements, not %u", digest);
-    if (count > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "hades_hash: at most 2^36 permutations per call");
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "hades_hash")) || (rc = sponge_check_rows(c, "hades_hash", arity, h->width - 1, h->width, digest)) ||
+        (rc = sponge_check_count(c, "hades_hash", count)))
+        return rc;
     if (!count) return GS_OK;
     if (!in || !out) return GS_ERR_ARG;
     gs_traffic(c, count * (arity + digest) * GS_ELT, count * hades_products(h), "k_hades_hash<%u>", h->width);
@@ -231,28 +194,28 @@ int gs_hades_hash(gs_ctx *c, const gs_hades *h, const void *in, uint64_t count, 
 }
 
 int gs_hades_merkle(gs_ctx *c, const gs_hades *h, const void *leaves, uint64_t n, uint32_t digest, void *nodes_out) {
-    if (!c || !h) return GS_ERR_ARG;
-    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "hades_merkle: the handle belongs to another context");
-    if (n < 2 || !gs_is_pow2(n) || n > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "hades_merkle: the number of leaves is a power of two, 2 .. 2^36");
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "hades_merkle")) || (rc = sponge_check_leaves(c, "hades_merkle", n))) return rc;
     if (digest < 1 || digest > 2 || 2 * digest >= h->width)
         return gs_fail(c, GS_ERR_ARG, "hades_merkle: nodes of %u elements (1 or 2): two of them do not fit a state of %u beside its capacity", digest, h->width);
     if (!leaves || !nodes_out) return GS_ERR_ARG;
     fe *nodes = (fe *)nodes_out;
     if (leaves != (const void *)(nodes + n * digest))
         GS_HIP(c, hipMemcpyAsync(nodes + n * digest, leaves, n * digest * GS_ELT, hipMemcpyDeviceToDevice, c->stream));
-    uint64_t cnt = n / 2;
-    for (; cnt > GS_HADES_BLOCK; cnt /= 2) {                                 // wide levels: the level below is the input matrix of a hash launch
-        gs_traffic(c, 3 * cnt * digest * GS_ELT, cnt * hades_products(h), "k_hades_merkle_level<%u>", h->width);
-        const int rc = launch_hash(c, h, nodes + 2 * cnt * digest, cnt, 2 * digest, digest, nodes + cnt * digest);
-        if (rc) return rc;
-    }
+    uint64_t cnt;
+    rc = sponge_tree_levels(nodes, n, digest, GS_HADES_BLOCK, &cnt, [&](const fe *below, uint64_t count, fe *level) {
+        gs_traffic(c, 3 * count * digest * GS_ELT, count * hades_products(h), "k_hades_merkle_level<%u>", h->width);
+        return launch_hash(c, h, below, count, 2 * digest, digest, level);
+    });
+    if (rc) return rc;
     gs_traffic(c, (4 * cnt - 1) * digest * GS_ELT, (2 * cnt - 1) * hades_products(h), "k_hades_merkle_top<%u>", h->width);
     return launch_top(c, h, nodes, (uint32_t)cnt, digest);
 }
 
 int gs_hades_merkle_paths(gs_ctx *c, const void *nodes, uint64_t n, uint32_t digest, const uint64_t *indexes_host, uint64_t count, void *out) {
     if (!c) return GS_ERR_ARG;
-    if (n < 2 || !gs_is_pow2(n) || n > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "hades_merkle_paths: the number of leaves is a power of two, 2 .. 2^36");
+    int rc = sponge_check_leaves(c, "hades_merkle_paths", n);
+    if (rc) return rc;
     if (digest < 1 || digest > 2) return gs_fail(c, GS_ERR_ARG, "hades_merkle_paths: nodes of 1 or 2 elements, not %u", digest);
     if (count > (1ull << 24)) return gs_fail(c, GS_ERR_ARG, "hades_merkle_paths: at most 2^24 paths per call");
     if (!count) return GS_OK;
@@ -263,8 +226,7 @@ int gs_hades_merkle_paths(gs_ctx *c, const void *nodes, uint64_t n, uint32_t dig
     const uint32_t depth = (uint32_t)gs_log2(n);
     const uint64_t total = count * (depth + 1) * digest;
     void *d_idx = nullptr;
-    int rc = gs_tmp_alloc(c, count * 8, &d_idx);
-    if (rc) return rc;
+    if ((rc = gs_tmp_alloc(c, count * 8, &d_idx))) return rc;
     if ((rc = gs_push(c, d_idx, indexes_host, count * 8)) == GS_OK) {
         hipLaunchKernelGGL(k_hades_paths, dim3(gs_grid(total)), dim3(256), 0, c->stream, (const fe *)nodes, n, depth, digest, (const uint64_t *)d_idx, total, (fe *)out);
         if (hipGetLastError() != hipSuccess) rc = gs_fail(c, GS_ERR_DEVICE, "hades_merkle_paths: launch failed");

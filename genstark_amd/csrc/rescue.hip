@@ -9,17 +9,17 @@
 //               squaring and size - 1 products); the window (1 .. 4 bits) is the one with the fewest products in all.  Every branch of
 //               the chain depends on the schedule alone: the same in every lane.  In the 128-bit flavour the chain runs on lazy
 //               five-limb values (gf128_lazy.h: lz_unpack once, lz_sqr / lz_mul_v, lz_pack once); every other flavour uses fe_mul.
-//   form 1      one thread per permutation (k_rescue_hash<W>): a workgroup's rows are one contiguous run of memory and pass through LDS
-//               both ways, like k_hades_hash's.  The W chains of a state run one after the other through ONE copy of the chain: the
+//   form 1      one thread per permutation (k_rescue_hash<W>): a workgroup's rows pass through LDS both ways (the staged row kernel
+//               body of sponge_common.h).  The W chains of a state run one after the other through ONE copy of the chain: the
 //               state is rotated by one element per pass, so every index into it is a constant.
 //   form 2      one lane per state element (k_rescue_spread<G>): a permutation is an aligned group of G = 2, 4 or 8 lanes (the width
 //               rounded up; surplus lanes carry zeros), every lane runs ONE chain, and for the matrix step a lane fetches the group's
 //               elements with cross-lane reads and computes its own row.  A permutation's latency is one chain per half round instead of
 //               W: this is the form of narrow launches, where the machine is empty and latency is all there is.
 //   tree        node i = element 0 of modifiedSponge(node 2i, node 2i + 1), heap layout: every level is one hash launch over the level
-//               below, ordered by the stream.  Workgroups are one wave in both forms, so a narrow level spreads over many CUs.
+//               below, ordered by the stream (the level loop of sponge_common.h, down to the root).  Workgroups are one wave in both forms, so a narrow level spreads over many CUs.
 //               Nothing here synchronises between workgroups.
-#include "common.h"
+#include "sponge_common.h"
 #include "../../include/gstark_rescue.h"
 #if defined(GS_FIELD_128)
 #include "gf128_lazy.h"
@@ -153,27 +153,7 @@ template <int W>
 __global__ __launch_bounds__(GS_RESCUE_BLOCK) void k_rescue_hash(const fe *__restrict__ in, uint64_t count, uint32_t arity, uint32_t digest, uint32_t modified,
                                                                  const fe *__restrict__ consts, uint32_t rounds, uint64_t alpha,
                                                                  const uint32_t *__restrict__ sched, uint32_t nops, uint32_t table, fe *__restrict__ out) {
-    __shared__ fe stage[GS_RESCUE_BLOCK * W];                               // rows x arity in, then rows x digest out
-    const uint32_t t = threadIdx.x;
-    const uint64_t first = (uint64_t)blockIdx.x * GS_RESCUE_BLOCK;
-    const uint32_t rows = count - first < GS_RESCUE_BLOCK ? (uint32_t)(count - first) : GS_RESCUE_BLOCK;
-    const fe *__restrict__ src = in + first * arity;
-    for (uint32_t k = t; k < rows * arity; k += GS_RESCUE_BLOCK) stage[k] = src[k];
-    __syncthreads();
-    fe s[W];
-    if (t < rows) {
-#pragma unroll
-        for (int j = 0; j < W; j++) s[j] = j < (int)arity ? stage[t * arity + j] : fe_zero();
-        rescue_permute<W>(s, consts, rounds, modified, alpha, sched, nops, table);
-    }
-    __syncthreads();                                                         // every row has been picked up: the stage takes the digests
-    if (t < rows) {
-        stage[t * digest] = s[0];
-        if (digest > 1) stage[t * digest + 1] = s[1];
-    }
-    __syncthreads();
-    fe *__restrict__ dst = out + first * digest;
-    for (uint32_t k = t; k < rows * digest; k += GS_RESCUE_BLOCK) dst[k] = stage[k];
+    GS_SPONGE_HASH_ROWS(GS_RESCUE_BLOCK, W, W, rescue_permute<W>(s, consts, rounds, modified, alpha, sched, nops, table));
 }
 
 __device__ __forceinline__ fe rescue_lane_read(const fe &a, int lane) {
@@ -215,8 +195,6 @@ __global__ __launch_bounds__(GS_RESCUE_BLOCK) void k_rescue_spread(const fe *__r
 
 namespace {
 
-#define GS_RESCUE_WIDTHS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-
 int launch_hash(gs_ctx *c, const gs_rescue *h, const fe *in, uint64_t count, uint32_t arity, uint32_t digest, uint32_t modified, uint32_t form, fe *out) {
     if (form == 2) {
         const uint32_t g = h->width <= 2 ? 2 : (h->width <= 4 ? 4 : 8);
@@ -236,7 +214,7 @@ int launch_hash(gs_ctx *c, const gs_rescue *h, const fe *in, uint64_t count, uin
         hipLaunchKernelGGL(k_rescue_hash<W>, dim3((unsigned)blocks), dim3(GS_RESCUE_BLOCK), 0, c->stream, in, count, arity, digest, modified,       \
                            (const fe *)h->consts, h->rounds, h->alpha, h->sched, h->nops, h->table, out);                                           \
         break;
-            GS_RESCUE_WIDTHS(X)
+            GS_SPONGE_WIDTHS(X)
 #undef X
         }
     }
@@ -311,39 +289,23 @@ int gs_rescue_create(gs_ctx *c, uint32_t width, uint32_t rounds, uint64_t alpha,
         const uint64_t cost = window_schedule(bits, w, ops, table);
         if (cost < best_cost) { best_cost = cost; best = ops; best_table = table; }
     }
-    uint64_t alpha_cost = 0;
-    for (uint64_t a = alpha; a > 1; a >>= 1) alpha_cost += 1 + (a & 1u);
     const uint64_t nkeys = (uint64_t)(2 * rounds + 3) * width, nmds = (uint64_t)width * width;
     void *p = nullptr;
-    int rc = gs_alloc(c, (nkeys + nmds) * GS_ELT + best.size() * 4, &p);
+    const int rc = sponge_upload(c, {{keys_host, nkeys * GS_ELT}, {mds_host, nmds * GS_ELT}, {best.data(), best.size() * 4}}, &p);
     if (rc) return rc;
     fe *consts = (fe *)p;
-    if ((rc = gs_push(c, consts, keys_host, nkeys * GS_ELT)) || (rc = gs_push(c, consts + nkeys, mds_host, nmds * GS_ELT)) ||
-        (rc = gs_push(c, consts + nkeys + nmds, best.data(), best.size() * 4))) {
-        gs_free(c, p);
-        return rc;
-    }
-    *out = new gs_rescue{c, width, rounds, alpha, (uint32_t)best.size(), best_table, best_cost, alpha_cost, consts, (const uint32_t *)(consts + nkeys + nmds)};
+    *out = new gs_rescue{c, width, rounds, alpha, (uint32_t)best.size(), best_table, best_cost, sponge_pow_products(alpha), consts, (const uint32_t *)(consts + nkeys + nmds)};
     return GS_OK;
 }
 
-int gs_rescue_destroy(gs_ctx *c, gs_rescue *h) {
-    if (!c) return GS_ERR_ARG;
-    if (!h) return GS_OK;
-    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "rescue_destroy: the handle belongs to another context");
-    gs_free(c, h->consts);                                                   // parked in the context's cache: launches already queued still read it in order
-    delete h;
-    return GS_OK;
-}
+int gs_rescue_destroy(gs_ctx *c, gs_rescue *h) { return sponge_destroy(c, h, "rescue_destroy"); }
 
 int gs_rescue_hash(gs_ctx *c, const gs_rescue *h, const void *in, uint64_t count, uint32_t arity, uint32_t digest, uint32_t modified, uint32_t form, void *out) {
-    if (!c || !h) return GS_ERR_ARG;
-    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "rescue_hash: the handle belongs to another context");
-    if (arity < 1 || arity > h->width) return gs_fail(c, GS_ERR_ARG, "rescue_hash: %u inputs do not fit a state of %u (1 .. %u)", arity, h->width, h->width);
-    if (digest < 1 || digest > 2) return gs_fail(c, GS_ERR_ARG, "rescue_hash: a digest of 1 or 2 elements, not %u", digest);
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "rescue_hash")) || (rc = sponge_check_rows(c, "rescue_hash", arity, h->width, h->width, digest))) return rc;
     if (modified > 1) return gs_fail(c, GS_ERR_ARG, "rescue_hash: modified is 0 (sponge) or 1 (modifiedSponge), not %u", modified);
     if (form > 2) return gs_fail(c, GS_ERR_ARG, "rescue_hash: form is 0 (chosen here), 1 (a thread per permutation) or 2 (a lane per element), not %u", form);
-    if (count > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "rescue_hash: at most 2^36 permutations per call");
+    if ((rc = sponge_check_count(c, "rescue_hash", count))) return rc;
     if (form == 2 && count > GS_RESCUE_SPREAD_MAX) return gs_fail(c, GS_ERR_ARG, "rescue_hash: form 2 serves at most 2^24 permutations per call");
     if (!count) return GS_OK;
     if (!in || !out) return GS_ERR_ARG;
@@ -353,21 +315,19 @@ int gs_rescue_hash(gs_ctx *c, const gs_rescue *h, const void *in, uint64_t count
 }
 
 int gs_rescue_merkle(gs_ctx *c, const gs_rescue *h, const void *leaves, uint64_t n, void *nodes_out) {
-    if (!c || !h) return GS_ERR_ARG;
-    if (h->ctx != c) return gs_fail(c, GS_ERR_ARG, "rescue_merkle: the handle belongs to another context");
-    if (n < 2 || !gs_is_pow2(n) || n > (1ull << 36)) return gs_fail(c, GS_ERR_ARG, "rescue_merkle: the number of leaves is a power of two, 2 .. 2^36");
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "rescue_merkle")) || (rc = sponge_check_leaves(c, "rescue_merkle", n))) return rc;
     if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_merkle: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
     if (!leaves || !nodes_out) return GS_ERR_ARG;
     fe *nodes = (fe *)nodes_out;
     if (leaves != (const void *)(nodes + n)) GS_HIP(c, hipMemcpyAsync(nodes + n, leaves, n * GS_ELT, hipMemcpyDeviceToDevice, c->stream));
     GS_HIP(c, hipMemsetAsync(nodes, 0, GS_ELT, c->stream));
-    for (uint64_t cnt = n / 2; cnt >= 1; cnt /= 2) {                         // the level below is the input matrix of a hash launch
-        const uint32_t form = pick_form(cnt, 0);
-        traffic(c, h, cnt, 2, 1, 1, form);
-        const int rc = launch_hash(c, h, nodes + 2 * cnt, cnt, 2, 1, 1, form, nodes + cnt);
-        if (rc) return rc;
-    }
-    return GS_OK;
+    uint64_t rest;
+    return sponge_tree_levels(nodes, n, 1, 0, &rest, [&](const fe *below, uint64_t count, fe *level) {
+        const uint32_t form = pick_form(count, 0);
+        traffic(c, h, count, 2, 1, 1, form);
+        return launch_hash(c, h, below, count, 2, 1, 1, form, level);
+    });
 }
 
 }  // extern "C"

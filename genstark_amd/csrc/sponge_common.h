@@ -1,0 +1,101 @@
+// sponge_common.h — what the algebraic hash units (hades.hip, rescue.hip) share: everything around a permutation.  A unit brings its
+// permutation, its parameter handle `H` (members `ctx` and `consts`, its one device block) and its launches.
+//   rows    a workgroup's BLOCK rows of `arity` elements are one contiguous run of memory: it is copied into LDS with consecutive lanes
+//           on consecutive elements, then every thread picks its row up from there; the digests leave the same way (GS_SPONGE_HASH_ROWS).
+//   tree    heap layout: the inputs of ALL nodes of one level are the level below, contiguous, in rows of 2 * digest elements — a level
+//           IS a hash launch (sponge_tree_levels).  The path gather reads nothing but a node array in that layout and belongs to no
+//           family: it is defined once, in hades.hip, under the name it was first exported with (gs_hades_merkle_paths).
+// Every message starts with the caller's name (`who`): the texts are those of the entry points.
+#pragma once
+#include "common.h"
+
+#include <initializer_list>
+
+#define GS_SPONGE_WIDTHS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)        // the state widths a unit instantiates: switch (width) { GS_SPONGE_WIDTHS(X) }
+
+// The body of a k_*_hash<W> kernel of BLOCK threads with the parameters `in`, `count`, `arity`, `digest` (1 or 2) and `out`: `count` rows of
+// `arity` elements in, `digest` elements out each, one workgroup per BLOCK rows.  PERMUTE is the call that permutes the state `fe s[W]`;
+// its constants are read at lane-independent indexes.  STAGE: elements of LDS per row (the widest arity the unit admits, at least 2 for
+// the digests).  A macro and no function: the permutation is inlined straight into the __global__ function, which compiles to what it
+// compiled to with the body written out in it (profiles/sponge_shared.md).
+#define GS_SPONGE_HASH_ROWS(BLOCK, W, STAGE, PERMUTE)                                                                                \
+    __shared__ fe stage[(BLOCK) * (STAGE)];                                    /* rows x arity in, then rows x digest out */         \
+    const uint32_t t = threadIdx.x;                                                                                                  \
+    const uint64_t first = (uint64_t)blockIdx.x * (BLOCK);                                                                           \
+    const uint32_t rows = count - first < (BLOCK) ? (uint32_t)(count - first) : (BLOCK);                                             \
+    const fe *__restrict__ src = in + first * arity;                                                                                 \
+    for (uint32_t k = t; k < rows * arity; k += (BLOCK)) stage[k] = src[k];                                                          \
+    __syncthreads();                                                                                                                 \
+    fe s[W];                                                                                                                         \
+    if (t < rows) {                                                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < W; j++) s[j] = j < (int)arity ? stage[t * arity + j] : fe_zero();                      \
+        PERMUTE;                                                                                                                     \
+    }                                                                                                                                \
+    __syncthreads();                                                         /* every row has been picked up: the stage takes the digests */ \
+    if (t < rows) {                                                                                                                  \
+        stage[t * digest] = s[0];                                                                                                    \
+        if (digest > 1) stage[t * digest + 1] = s[1];                                                                                \
+    }                                                                                                                                \
+    __syncthreads();                                                                                                                 \
+    fe *__restrict__ dst = out + first * digest;                                                                                     \
+    for (uint32_t k = t; k < rows * digest; k += (BLOCK)) dst[k] = stage[k]
+
+template <class H>
+static inline int sponge_check_handle(gs_ctx *c, const H *h, const char *who) {
+    if (!c || !h) return GS_ERR_ARG;
+    return h->ctx == c ? GS_OK : gs_fail(c, GS_ERR_ARG, "%s: the handle belongs to another context", who);
+}
+
+// a hash launch: rows of 1 .. max_arity inputs into a state of `width`, 1 or 2 elements out; `count` of them (a check of its own: a
+// unit has checks of its own arguments to make between the two)
+static inline int sponge_check_rows(gs_ctx *c, const char *who, uint32_t arity, uint32_t max_arity, uint32_t width, uint32_t digest) {
+    if (arity < 1 || arity > max_arity) return gs_fail(c, GS_ERR_ARG, "%s: %u inputs do not fit a state of %u (1 .. %u)", who, arity, width, max_arity);
+    return digest >= 1 && digest <= 2 ? GS_OK : gs_fail(c, GS_ERR_ARG, "%s: a digest of 1 or 2 elements, not %u", who, digest);
+}
+static inline int sponge_check_count(gs_ctx *c, const char *who, uint64_t count) {
+    return count <= (1ull << 36) ? GS_OK : gs_fail(c, GS_ERR_ARG, "%s: at most 2^36 permutations per call", who);
+}
+
+static inline int sponge_check_leaves(gs_ctx *c, const char *who, uint64_t n) {
+    return n >= 2 && gs_is_pow2(n) && n <= (1ull << 36) ? GS_OK : gs_fail(c, GS_ERR_ARG, "%s: the number of leaves is a power of two, 2 .. 2^36", who);
+}
+
+// products of one x^alpha: the squarings and products fe_pow_u64 makes — none by one at the start, none after the top bit
+static inline uint64_t sponge_pow_products(uint64_t alpha) {
+    uint64_t n = 0;
+    for (uint64_t e = alpha; e > 1; e >>= 1) n += 1 + (e & 1u);
+    return n;
+}
+
+// the constants of a parameter set: ONE device block that holds the host parts one after the other
+struct sponge_part { const void *host; uint64_t bytes; };
+static inline int sponge_upload(gs_ctx *c, std::initializer_list<sponge_part> parts, void **out) {
+    uint64_t total = 0, at = 0;
+    for (const sponge_part &part : parts) total += part.bytes;
+    int rc = gs_alloc(c, total, out);
+    for (const sponge_part &part : parts) {
+        if (!rc) rc = gs_push(c, (uint8_t *)*out + at, part.host, part.bytes);
+        at += part.bytes;
+    }
+    if (rc && *out) gs_free(c, *out);
+    return rc;
+}
+
+template <class H>
+static inline int sponge_destroy(gs_ctx *c, H *h, const char *who) {
+    if (!c || !h) return c ? GS_OK : GS_ERR_ARG;
+    const int rc = sponge_check_handle(c, h, who);
+    if (rc) return rc;
+    gs_free(c, h->consts);                                                   // parked in the context's cache: launches already queued still read it in order
+    delete h;
+    return GS_OK;
+}
+
+// The levels of more than `top` nodes, from the widest down: level(below, cnt, here) hashes the cnt rows of 2 * digest elements at
+// `below` into the cnt nodes at `here`; the stream orders the launches.  -> *rest: the nodes of the first level left to the caller
+template <class Level>
+static inline int sponge_tree_levels(fe *nodes, uint64_t n, uint32_t digest, uint64_t top, uint64_t *rest, Level level) {
+    int rc = GS_OK;
+    for (*rest = n / 2; *rest > top && !rc; *rest /= 2) rc = level((const fe *)(nodes + 2 * *rest * digest), *rest, nodes + *rest * digest);
+    return rc;
+}

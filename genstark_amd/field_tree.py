@@ -1,0 +1,149 @@
+"""What the algebraic hash families (hades.py, rescue_hash.py) share above the C ABI, as csrc/sponge_common.h is below it: a parameter
+set with a device handle, and the heap-layout Merkle tree of nodes of `digest` field elements with its authentication paths.  On a
+backend whose library lacks the entry points (the tests' double) everything is computed on host integers and gives the same values."""
+import ctypes as C
+
+from ._abi import GstarkError
+from .field import Matrix, Vector
+
+
+class DeviceParameters:
+    """A parameter set whose constants live on the field's context once they are needed.  A subclass names itself (`_who`, the front of
+    every message) and its entry points (`_family`: gs_<family>_*), and has `_maxArity` and `_create(out)` (the upload)."""
+    _who = _family = _handle = None
+
+    @property
+    def onDevice(self):
+        be = getattr(self.field, 'backend', None)              # a HostField has none
+        return be is not None and hasattr(be.lib, f'gs_{self._family}_hash')
+
+    def handle(self):
+        """the gs_<family> of this parameter set on the field's context: constants uploaded once, on first use"""
+        if self._handle is None:
+            h = C.c_void_p()
+            self._create(C.byref(h))
+            self._handle = h
+        return self._handle
+
+    def __del__(self):
+        try:
+            if self._handle is not None and self.field.backend.ctx:
+                getattr(self.field.backend.lib, f'gs_{self._family}_destroy')(self.field.backend.ctx, self._handle)
+            self._handle = None
+        except Exception:
+            pass
+
+    def _hashRows(self, rows, digest, host_row, *options, check=None):
+        """hashMany: host_row(row) is the final state on host integers, options what gs_<family>_hash takes between `digest` and `out`,
+        check() the subclass's own refusals (their place is after the digest's)"""
+        f, be = self.field, self.field.backend
+        if digest not in (1, 2):
+            raise GstarkError(f'{self._who}: a digest of 1 or 2 elements, not {digest}')
+        if check:
+            check()
+        if not isinstance(rows, Matrix):
+            rows = [list(r) for r in rows]
+            if any(len(r) != len(rows[0]) for r in rows):
+                raise GstarkError(f'{self._who}: every row has the same number of inputs')
+        count, arity = (rows.rowCount, rows.colCount) if isinstance(rows, Matrix) else (len(rows), len(rows[0]) if rows else 1)
+        if not 0 < arity <= self._maxArity:
+            raise GstarkError(f'{self._who}: {arity} inputs do not fit a state of {self.width} (1 .. {self._maxArity})')
+        if not self.onDevice:
+            values = rows.toValues() if isinstance(rows, Matrix) else rows
+            return f.newMatrixFrom([host_row(r)[:digest] for r in values]) if count else Matrix(be, 0, digest)
+        src = rows if isinstance(rows, Matrix) or not count else f.newMatrixFrom(rows)
+        out = Matrix(be, count, digest)
+        if count:
+            be.call(f'gs_{self._family}_hash', self.handle(), C.c_void_p(src.ptr), count, arity, digest, *options, C.c_void_p(out.ptr))
+        return out
+
+
+def verify_path(root, index, proof, node):
+    """a path (the leaf, then its siblings bottom-up) against a root: node(left, right) level by level, sides by the index bits"""
+    index += 1 << (len(proof) - 1)
+    v = proof[0]
+    for sibling in proof[1:]:
+        v = node(sibling, v) if index & 1 else node(v, sibling)
+        index >>= 1
+    return root == v
+
+
+class FieldMerkleTree:
+    """2n nodes of `digest` elements in the heap layout: leaves at n .. 2n - 1, root at 1, node 0 unused.  leaves: a device Matrix of
+    n x digest (a Vector of n for digest=1) — then nothing goes through host integers —, or n host values.  A subclass names itself
+    (`_who`) and has `_newNodes(count)` (the kind of array deviceNodes is), `_buildOnDevice(src, out)` and `_node(left, right)` on host
+    integers.  The path gather is the family-neutral one (gs_hades_merkle_paths reads nothing but the node array)."""
+    _unreadable = [[]]                       # what leaves that cannot be read as host values count as
+
+    def __init__(self, hash, leaves, digest):
+        f = hash.field
+        self.hash, self.field, self.digest = hash, f, digest
+        if isinstance(leaves, Vector):
+            if digest != 1:
+                raise GstarkError(f'{self._who}: a Vector holds leaves of one element (digest=1)')
+            n = leaves.length
+        elif isinstance(leaves, Matrix):
+            if leaves.colCount != digest:
+                raise GstarkError(f'{self._who}: the leaf matrix has {leaves.colCount} columns, the nodes {digest} elements')
+            n = leaves.rowCount
+        else:
+            try:
+                leaves = [[int(v) % f.modulus] for v in leaves] if digest == 1 else [[int(v) % f.modulus for v in leaf] for leaf in leaves]
+            except TypeError:
+                leaves = self._unreadable
+            if any(len(leaf) != digest for leaf in leaves):
+                raise GstarkError(f'{self._who}: every leaf has {digest} elements')
+            n = len(leaves)
+        if n < 2 or n & (n - 1):
+            raise GstarkError(f'{self._who}: {n} leaves: the number of leaves is a power of two, at least 2')
+        self.leafCount, self.depth = n, n.bit_length() - 1
+        self._host = self.deviceNodes = None      # deviceNodes: the 2n nodes on the device (None on a library without the entry points)
+        if hash.onDevice:
+            src = leaves if isinstance(leaves, (Matrix, Vector)) else f.newMatrixFrom(leaves)
+            self.deviceNodes = self._newNodes(2 * n)
+            self._buildOnDevice(src, self.deviceNodes)
+        else:
+            if isinstance(leaves, (Matrix, Vector)):
+                leaves = _rows(leaves)
+            nodes = [[0] * digest] * n + leaves
+            for i in range(n - 1, 0, -1):
+                nodes[i] = self._node(nodes[2 * i], nodes[2 * i + 1])
+            self._host = nodes
+
+    def _shape(self, node):                  # a node as the reference's classes hold it: a pair, or one integer
+        return node[0] if self.digest == 1 else tuple(node)
+
+    @property
+    def nodes(self):
+        """every node on the host, as the reference's `nodes`: index 0 is unused (None)"""
+        rows = self._host if self.deviceNodes is None else _rows(self.deviceNodes)
+        return [None] + [self._shape(r) for r in rows[1:]]
+
+    @property
+    def root(self):
+        d = self.deviceNodes
+        return self._shape(self._host[1] if d is None else [d.getValue(1)] if isinstance(d, Vector) else d.row(1).toValues())
+
+    def prove(self, index):
+        return self.proveMany([index])[0]
+
+    def proveMany(self, indexes):
+        """prove(index) for every index (repeats allowed): per path the leaf, then its siblings bottom-up.  One launch and one read-back."""
+        indexes = [int(i) for i in indexes]
+        n, d, per = self.leafCount, self.digest, self.depth + 1
+        if self.deviceNodes is None:
+            if any(not 0 <= i < n for i in indexes):
+                raise GstarkError(f'{self._who}: an index is outside of the {n} leaves')
+            return [[self._shape(self._host[n + i])] + [self._shape(self._host[((n + i) >> l) ^ 1]) for l in range(self.depth)] for i in indexes]
+        if any(i < 0 for i in indexes):
+            raise GstarkError(f'{self._who}: an index is outside of the {n} leaves')
+        if not indexes:
+            return []
+        out = self._newNodes(len(indexes) * per)
+        self.field.backend.call('gs_hades_merkle_paths', C.c_void_p(self.deviceNodes.ptr), n, d, (C.c_uint64 * len(indexes))(*indexes), len(indexes), C.c_void_p(out.ptr))
+        rows = _rows(out)
+        return [[self._shape(r) for r in rows[k * per:(k + 1) * per]] for k in range(len(indexes))]
+
+
+def _rows(array):                            # the nodes of a device array as rows of `digest` integers
+    return array.toValues() if isinstance(array, Matrix) else [[v] for v in array.toValues()]

@@ -3,22 +3,21 @@
 `HadesHash` is `createHash` of the reference's examples/poseidon/utils.ts:19-49, `HadesMerkleTree` its `MerkleTree` (digest=2: nodes of
 two elements, :126-167) and `MerkleTree2` (digest=1, :169-210): the same values in the same orders.  `hash(inputs)` is host integer
 arithmetic like the example's function; `hashMany`, the tree and its paths are one launch each on the context's stream (a tree: one per
-wide level and one for the top), with one read-back for any number of paths.
-
-On a backend whose library lacks the entry points (the tests' double) everything is computed on host integers instead and gives the
-same values: the layer above the kernels is testable without a GPU.  The product's library has them.
-"""
+wide level and one for the top), with one read-back for any number of paths.  What is not Poseidon's own is field_tree.py, the host
+fallback on a library without the entry points included."""
 import ctypes as C
 
 from ._abi import GstarkError
-from .field import Matrix, Vector
+from .field import Matrix
+from .field_tree import DeviceParameters, FieldMerkleTree, verify_path
 from .poseidon import mds_matrix, round_constants as derived_round_constants
 
 
-class HadesHash:
+class HadesHash(DeviceParameters):
     """createHash(field, exp, rf, rp, stateWidth, rc?) — utils.ts:19.  round_constants: (rf + rp) rows of `width` values; mds: `width`
     rows of `width` values; both derived as the example derives them (sha256 over 'Hades<c>', the Cauchy matrix of 'HadesMDSx<i>' and
     'HadesMDSy<j>') when omitted."""
+    _who, _family = 'HadesHash', 'hades'
 
     def __init__(self, field, alpha, full_rounds, partial_rounds, width, round_constants=None, mds=None):
         alpha, rf, rp, width = int(alpha), int(full_rounds), int(partial_rounds), int(width)
@@ -36,8 +35,7 @@ class HadesHash:
         if len(m) != width or any(len(row) != width for row in m):
             raise GstarkError(f'HadesHash: the matrix has {width} rows of {width} values')
         self.field, self.alpha, self.fullRounds, self.partialRounds, self.width = field, alpha, rf, rp, width
-        self.roundConstants, self.mds = rc, m
-        self._handle = None
+        self.roundConstants, self.mds, self._maxArity = rc, m, width - 1
 
     # ---- host integers
     def permute(self, state):
@@ -60,144 +58,40 @@ class HadesHash:
 
     __call__ = hash
 
-    # ---- device
-    @property
-    def onDevice(self):
-        return hasattr(self.field.backend.lib, 'gs_hades_hash')
-
-    def handle(self):
-        """the gs_hades of this parameter set on the field's context: constants uploaded once, on first use"""
-        if self._handle is None:
-            f, be = self.field, self.field.backend
-            h = C.c_void_p()
-            be.call('gs_hades_create', self.width, self.fullRounds, self.partialRounds, self.alpha,
-                    b''.join(f.le(v) for row in self.roundConstants for v in row), b''.join(f.le(v) for row in self.mds for v in row), C.byref(h))
-            self._handle = h
-        return self._handle
-
-    def __del__(self):
-        try:
-            be = self.field.backend
-            if self._handle is not None and be.ctx:
-                be.lib.gs_hades_destroy(be.ctx, self._handle)
-            self._handle = None
-        except Exception:
-            pass
+    # ---- device (field_tree.DeviceParameters)
+    def _create(self, out):
+        f = self.field
+        f.backend.call('gs_hades_create', self.width, self.fullRounds, self.partialRounds, self.alpha,
+                       b''.join(f.le(v) for row in self.roundConstants for v in row), b''.join(f.le(v) for row in self.mds for v in row), out)
 
     def hashMany(self, rows, digest=2):
         """One permutation per row of `rows` (a device Matrix, or rows of integers of one length): a Matrix of len(rows) x digest."""
-        f, be = self.field, self.field.backend
-        if digest not in (1, 2):
-            raise GstarkError(f'HadesHash: a digest of 1 or 2 elements, not {digest}')
-        if not isinstance(rows, Matrix):
-            rows = [list(r) for r in rows]
-            if any(len(r) != len(rows[0]) for r in rows):
-                raise GstarkError('HadesHash: every row has the same number of inputs')
-        count, arity = (rows.rowCount, rows.colCount) if isinstance(rows, Matrix) else (len(rows), len(rows[0]) if rows else 1)
-        if not 0 < arity < self.width:
-            raise GstarkError(f'HadesHash: {arity} inputs do not fit a state of {self.width} (1 .. {self.width - 1})')
-        if not self.onDevice:
-            values = rows.toValues() if isinstance(rows, Matrix) else rows
-            return f.newMatrixFrom([self.hash(r)[:digest] for r in values]) if count else Matrix(be, 0, digest)
-        src = rows if isinstance(rows, Matrix) or not count else f.newMatrixFrom(rows)
-        out = Matrix(be, count, digest)
-        if count:
-            be.call('gs_hades_hash', self.handle(), C.c_void_p(src.ptr), count, arity, digest, C.c_void_p(out.ptr))
-        return out
+        return self._hashRows(rows, digest, self.hash)
 
 
-class HadesMerkleTree:
+class HadesMerkleTree(FieldMerkleTree):
     """MerkleTree (digest=2) / MerkleTree2 (digest=1) of utils.ts over `hash`: 2n x digest elements in the heap layout, leaves at
     n .. 2n - 1, root at 1.  leaves: a device Matrix of n x digest (a Vector of n for digest=1) — then nothing goes through host integers
-    —, or a list of n pairs (digest=2) / n integers (digest=1)."""
+    —, or a list of n pairs (digest=2) / n integers (digest=1).  deviceNodes is the 2n x digest Matrix."""
+    _who = 'HadesMerkleTree'
 
     def __init__(self, hash, leaves, digest):
-        f = hash.field
         if digest not in (1, 2) or 2 * digest >= hash.width:
             raise GstarkError(f'HadesMerkleTree: nodes of {digest} elements (1 or 2): two of them do not fit a state of {hash.width} beside its capacity')
-        self.hash, self.field, self.digest = hash, f, digest
-        if isinstance(leaves, Vector):
-            if digest != 1:
-                raise GstarkError('HadesMerkleTree: a Vector holds leaves of one element (digest=1)')
-            n = leaves.length
-        elif isinstance(leaves, Matrix):
-            if leaves.colCount != digest:
-                raise GstarkError(f'HadesMerkleTree: the leaf matrix has {leaves.colCount} columns, the nodes {digest} elements')
-            n = leaves.rowCount
-        else:
-            try:
-                leaves = [[int(v)] for v in leaves] if digest == 1 else [[int(v) for v in leaf] for leaf in leaves]
-            except TypeError:
-                leaves = [[]]
-            if any(len(leaf) != digest for leaf in leaves):
-                raise GstarkError(f'HadesMerkleTree: every leaf has {digest} elements')
-            n = len(leaves)
-        if n < 2 or n & (n - 1):
-            raise GstarkError(f'HadesMerkleTree: {n} leaves: the number of leaves is a power of two, at least 2')
-        self.leafCount, self.depth = n, n.bit_length() - 1
-        self._host = self._device = None
-        if hash.onDevice:
-            src = leaves if isinstance(leaves, (Matrix, Vector)) else f.newMatrixFrom(leaves)
-            self._device = Matrix(f.backend, 2 * n, digest)
-            f.backend.call('gs_hades_merkle', hash.handle(), C.c_void_p(src.ptr), n, digest, C.c_void_p(self._device.ptr))
-        else:
-            if isinstance(leaves, Vector):
-                leaves = [[v] for v in leaves.toValues()]
-            elif isinstance(leaves, Matrix):
-                leaves = leaves.toValues()
-            nodes = [[0] * digest] * n + [[v % f.modulus for v in leaf] for leaf in leaves]
-            for i in range(n - 1, 0, -1):
-                nodes[i] = hash.hash(nodes[2 * i] + nodes[2 * i + 1])[:digest]
-            self._host = nodes
+        super().__init__(hash, leaves, digest)
 
-    def _shape(self, node):                  # a node as the reference's classes hold it: a pair, or one integer
-        return node[0] if self.digest == 1 else tuple(node)
+    def _newNodes(self, count):
+        return Matrix(self.field.backend, count, self.digest)
 
-    @property
-    def deviceNodes(self):
-        """the 2n x digest Matrix of the tree on the device (None on a library without the entry points)"""
-        return self._device
+    def _buildOnDevice(self, src, out):
+        self.field.backend.call('gs_hades_merkle', self.hash.handle(), C.c_void_p(src.ptr), self.leafCount, self.digest, C.c_void_p(out.ptr))
 
-    @property
-    def nodes(self):
-        """every node on the host, as the reference's `nodes`: index 0 is unused (None)"""
-        rows = self._host if self._device is None else self._device.toValues()
-        return [None] + [self._shape(r) for r in rows[1:]]
-
-    @property
-    def root(self):
-        return self._shape(self._host[1] if self._device is None else self._device.row(1).toValues())
-
-    def prove(self, index):
-        return self.proveMany([index])[0]
-
-    def proveMany(self, indexes):
-        """prove(index) for every index (repeats allowed): per path the leaf, then its siblings bottom-up.  One launch and one read-back."""
-        indexes = [int(i) for i in indexes]
-        n, d, per = self.leafCount, self.digest, self.depth + 1
-        if self._device is None:
-            if any(not 0 <= i < n for i in indexes):
-                raise GstarkError(f'HadesMerkleTree: an index is outside of the {n} leaves')
-            return [[self._shape(self._host[n + i])] + [self._shape(self._host[((n + i) >> l) ^ 1]) for l in range(self.depth)] for i in indexes]
-        if any(i < 0 for i in indexes):
-            raise GstarkError(f'HadesMerkleTree: an index is outside of the {n} leaves')
-        if not indexes:
-            return []
-        f = self.field
-        out = Matrix(f.backend, len(indexes) * per, d)
-        f.backend.call('gs_hades_merkle_paths', C.c_void_p(self._device.ptr), n, d, (C.c_uint64 * len(indexes))(*indexes), len(indexes), C.c_void_p(out.ptr))
-        rows = out.toValues()
-        return [[self._shape(r) for r in rows[k * per:(k + 1) * per]] for k in range(len(indexes))]
+    def _node(self, left, right):
+        return self.hash.hash(left + right)[:self.digest]
 
     @staticmethod
     def verify(root, index, proof, hash):
         """utils.ts:151-166 / :194-209 — the shape of the nodes (pairs or single integers) is the proof's"""
-        single = isinstance(proof[0], int)
-        take = (lambda v: v[0]) if single else (lambda v: tuple(v[:2]))
-        listed = (lambda v: [v]) if single else list
-        index += 1 << (len(proof) - 1)
-        v = proof[0]
-        for sibling in proof[1:]:
-            v = take(hash(listed(sibling) + listed(v))) if index & 1 else take(hash(listed(v) + listed(sibling)))
-            index >>= 1
-        return (root if single else tuple(root)) == v
+        if isinstance(proof[0], int):
+            return verify_path(root, index, proof, lambda left, right: hash([left, right])[0])
+        return verify_path(tuple(root), index, proof, lambda left, right: tuple(hash(list(left) + list(right))[:2]))

@@ -5,25 +5,23 @@ statement over them.
 `RescueMerkleTree` its `MerkleTree` (:232-273): the same values in the same orders.  `sponge`, `modifiedSponge` and `hash2` are host
 integer arithmetic like the example's; `hashMany`, the tree and its paths run on the context's stream (a tree: one launch per level),
 with one read-back for any number of paths.  `rescue_merkle_proof_air` is the RescueMP script of examples/rescue/merkleProof.ts:51-146 as
-a GenericAir.
-
-On a backend whose library lacks the entry points (the tests' double) everything is computed on host integers instead and gives the
-same values: the layer above the kernels is testable without a GPU.  The product's library has them.
-"""
+a GenericAir.  What is not Rescue's own is field_tree.py, the host fallback on a library without the entry points included."""
 import ctypes as C
 
 from . import rescue as _params
 from ._abi import GstarkError
 from .air_generic import GenericAir, mat_vec
 from .field import Matrix, Vector
+from .field_tree import DeviceParameters, FieldMerkleTree, verify_path
 
 STEPS_PER_HASH = 32
 
 
-class RescueHash:
+class RescueHash(DeviceParameters):
     """new Rescue(field, alpha, invAlpha, registers, rounds, mds, constants) — utils.ts:33.  inv_alpha may be negative, as in the
     examples: x^inv_alpha is then (1/x)^|inv_alpha|, which is x^(p - 1 - |inv_alpha|) for every x, 0 included (0 -> 0).  constants:
     width initial, width x width matrix and width additive key constants, flat (splitConstants, :204-227)."""
+    _who, _family = 'RescueHash', 'rescue'
 
     def __init__(self, field, alpha, inv_alpha, width, rounds, mds, constants):
         alpha, inv_alpha, width, rounds = int(alpha), int(inv_alpha), int(width), int(rounds)
@@ -49,7 +47,7 @@ class RescueHash:
         self.field, self.alpha, self.invAlpha, self.invExponent, self.width, self.rounds, self.mds = field, alpha, inv_alpha, exponent, width, rounds, m
         self.iConstants, self.cConstants = c[:width], c[width + width * width:]
         self.cMatrix = [c[width + i * width:width + (i + 1) * width] for i in range(width)]
-        self._keys = self._handle = None
+        self._keys, self._maxArity = None, width
 
     # ---- host integers
     def _mmul(self, m, v):
@@ -124,133 +122,46 @@ class RescueHash:
         """makeHashFunction (utils.ts:11-15)"""
         return self.modifiedSponge([v1, v2] + [0] * (self.width - 2))[0][0]
 
-    # ---- device
-    @property
-    def onDevice(self):
-        be = getattr(self.field, 'backend', None)              # a HostField has none
-        return be is not None and hasattr(be.lib, 'gs_rescue_hash')
-
-    def handle(self):
-        """the gs_rescue of this parameter set on the field's context: constants and exponent schedule made once, on first use"""
-        if self._handle is None:
-            f, be = self.field, self.field.backend
-            h = C.c_void_p()
-            be.call('gs_rescue_create', self.width, self.rounds, self.alpha, f.le(self.invExponent), b''.join(f.le(v) for row in self.mds for v in row),
-                    b''.join(f.le(v) for row in self.keys for v in row), C.byref(h))
-            self._handle = h
-        return self._handle
-
-    def __del__(self):
-        try:
-            be = self.field.backend
-            if self._handle is not None and be is not None and be.ctx:
-                be.lib.gs_rescue_destroy(be.ctx, self._handle)
-            self._handle = None
-        except Exception:
-            pass
+    # ---- device (field_tree.DeviceParameters)
+    def _create(self, out):
+        f = self.field
+        f.backend.call('gs_rescue_create', self.width, self.rounds, self.alpha, f.le(self.invExponent), b''.join(f.le(v) for row in self.mds for v in row),
+                       b''.join(f.le(v) for row in self.keys for v in row), out)
 
     def hashMany(self, rows, digest=1, modified=True, form=0):
         """One permutation per row of `rows` (a device Matrix, or rows of integers of one length): a Matrix of len(rows) x digest, the
         leading elements of the final states.  form: 0 the library chooses, 1 a thread per permutation, 2 a lane per state element."""
-        f, be = self.field, self.field.backend
-        if digest not in (1, 2):
-            raise GstarkError(f'RescueHash: a digest of 1 or 2 elements, not {digest}')
-        if form not in (0, 1, 2):
-            raise GstarkError(f'RescueHash: form is 0, 1 or 2, not {form}')
-        if not isinstance(rows, Matrix):
-            rows = [list(r) for r in rows]
-            if any(len(r) != len(rows[0]) for r in rows):
-                raise GstarkError('RescueHash: every row has the same number of inputs')
-        count, arity = (rows.rowCount, rows.colCount) if isinstance(rows, Matrix) else (len(rows), len(rows[0]) if rows else 1)
-        if not 0 < arity <= self.width:
-            raise GstarkError(f'RescueHash: {arity} inputs do not fit a state of {self.width} (1 .. {self.width})')
-        if not self.onDevice:
-            values = rows.toValues() if isinstance(rows, Matrix) else rows
-            run = self.modifiedSponge if modified else self.sponge
-            return f.newMatrixFrom([run(r)[1][-1][:digest] for r in values]) if count else Matrix(be, 0, digest)
-        src = rows if isinstance(rows, Matrix) or not count else f.newMatrixFrom(rows)
-        out = Matrix(be, count, digest)
-        if count:
-            be.call('gs_rescue_hash', self.handle(), C.c_void_p(src.ptr), count, arity, digest, 1 if modified else 0, form, C.c_void_p(out.ptr))
-        return out
+        def check():
+            if form not in (0, 1, 2):
+                raise GstarkError(f'RescueHash: form is 0, 1 or 2, not {form}')
+        run = self.modifiedSponge if modified else self.sponge
+        return self._hashRows(rows, digest, lambda r: run(r)[1][-1], 1 if modified else 0, form, check=check)
 
 
-class RescueMerkleTree:
+class RescueMerkleTree(FieldMerkleTree):
     """MerkleTree of utils.ts:232-273 over hash.hash2: 2n elements in the heap layout, leaves at n .. 2n - 1, root at 1.  leaves: a device
-    Vector of n elements — then nothing goes through host integers —, or n integers."""
+    Vector of n elements — then nothing goes through host integers —, or n integers.  deviceNodes is the Vector of 2n nodes."""
+    _who = 'RescueMerkleTree'
+    _unreadable = []                         # leaves that are no integers are no leaves: the message of the leaf count
 
     def __init__(self, hash, leaves):
-        f = hash.field
         if hash.width < 3:
             raise GstarkError(f'RescueMerkleTree: two nodes do not fit a state of {hash.width} beside its capacity (width 3 .. 8)')
-        self.hash, self.field = hash, f
-        if isinstance(leaves, Vector):
-            n = leaves.length
-        else:
-            try:
-                leaves = [int(v) % f.modulus for v in leaves]
-            except TypeError:
-                leaves = []
-            n = len(leaves)
-        if n < 2 or n & (n - 1):
-            raise GstarkError(f'RescueMerkleTree: {n} leaves: the number of leaves is a power of two, at least 2')
-        self.leafCount, self.depth = n, n.bit_length() - 1
-        self._host = self._device = None
-        if hash.onDevice:
-            src = leaves if isinstance(leaves, Vector) else f.newVectorFrom(leaves)
-            self._device = Vector(f.backend, 2 * n)
-            f.backend.call('gs_rescue_merkle', hash.handle(), C.c_void_p(src.ptr), n, C.c_void_p(self._device.ptr))
-        else:
-            nodes = [0] * n + (leaves.toValues() if isinstance(leaves, Vector) else leaves)
-            for i in range(n - 1, 0, -1):
-                nodes[i] = hash.hash2(nodes[2 * i], nodes[2 * i + 1])
-            self._host = nodes
+        super().__init__(hash, () if isinstance(leaves, Matrix) else leaves, 1)      # a Matrix is no leaves here: the message of the leaf count
 
-    @property
-    def deviceNodes(self):
-        """the Vector of 2n nodes on the device (None on a library without the entry points)"""
-        return self._device
+    def _newNodes(self, count):
+        return Vector(self.field.backend, count)
 
-    @property
-    def nodes(self):
-        """every node on the host, as the reference's `nodes`: index 0 is unused (None)"""
-        values = self._host if self._device is None else self._device.toValues()
-        return [None] + list(values[1:])
+    def _buildOnDevice(self, src, out):
+        self.field.backend.call('gs_rescue_merkle', self.hash.handle(), C.c_void_p(src.ptr), self.leafCount, C.c_void_p(out.ptr))
 
-    @property
-    def root(self):
-        return self._host[1] if self._device is None else self._device.getValue(1)
-
-    def prove(self, index):
-        return self.proveMany([index])[0]
-
-    def proveMany(self, indexes):
-        """prove(index) for every index (repeats allowed): per path the leaf, then its siblings bottom-up.  One launch and one read-back."""
-        indexes = [int(i) for i in indexes]
-        n, per = self.leafCount, self.depth + 1
-        if self._device is None:
-            if any(not 0 <= i < n for i in indexes):
-                raise GstarkError(f'RescueMerkleTree: an index is outside of the {n} leaves')
-            return [[self._host[n + i]] + [self._host[((n + i) >> l) ^ 1] for l in range(self.depth)] for i in indexes]
-        if any(i < 0 for i in indexes):
-            raise GstarkError(f'RescueMerkleTree: an index is outside of the {n} leaves')
-        if not indexes:
-            return []
-        be = self.field.backend
-        out = Vector(be, len(indexes) * per)
-        be.call('gs_hades_merkle_paths', C.c_void_p(self._device.ptr), n, 1, (C.c_uint64 * len(indexes))(*indexes), len(indexes), C.c_void_p(out.ptr))
-        values = out.toValues()
-        return [values[k * per:(k + 1) * per] for k in range(len(indexes))]
+    def _node(self, left, right):
+        return [self.hash.hash2(left[0], right[0])]
 
     @staticmethod
     def verify(root, index, proof, hash2):
         """utils.ts:257-272"""
-        index += 1 << (len(proof) - 1)
-        v = proof[0]
-        for sibling in proof[1:]:
-            v = hash2(sibling, v) if index & 1 else hash2(v, sibling)
-            index >>= 1
-        return root == v
+        return verify_path(root, index, proof, hash2)
 
 
 def rescue4x128(field):

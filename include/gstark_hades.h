@@ -40,9 +40,11 @@ int gs_hades_hash(gs_ctx *ctx, const gs_hades *h, const void *in, uint64_t count
 int gs_hades_merkle(gs_ctx *ctx, const gs_hades *h, const void *leaves, uint64_t n, uint32_t digest, void *nodes_out);
 uint32_t gs_hades_merkle_top(void);
 
-/* The authentication paths of `count` leaves (indexes_host[k] < n; repeats allowed) out of a tree of gs_hades_merkle: out (device)
+/* The authentication paths of `count` leaves (indexes_host[k] < n; repeats allowed) out of a tree in the heap layout above: out (device)
  * receives count x (log2 n + 1) x digest elements, per path the leaf and its log2 n siblings bottom-up — the order of
- * MerkleTree.prove(index) — so that one read-back serves any number of paths. */
+ * MerkleTree.prove(index) — so that one read-back serves any number of paths.  The gather is family-neutral: it reads nothing but the
+ * node array and hashes nothing, so it serves the trees of gs_hades_merkle and of gs_rescue_merkle (gstark_rescue.h, digest = 1) alike;
+ * the name is the one it was first exported with. */
 int gs_hades_merkle_paths(gs_ctx *ctx, const void *nodes, uint64_t n, uint32_t digest, const uint64_t *indexes_host, uint64_t count, void *out);
 
 #ifdef __cplusplus

@@ -13,7 +13,8 @@
  *
  * The tree is the reference's MerkleTree (utils.ts:232-273) over makeHashFunction (:11-15) in its heap layout: 2n elements, the leaves
  * at nodes n .. 2n - 1, node i = element 0 of modifiedSponge([node 2i, node 2i + 1, 0, ...]), the root at 1, node 0 zero.
- * Authentication paths come from gs_hades_merkle_paths (gstark_hades.h) with digest = 1: it reads nothing but the node array.
+ * Authentication paths come from gs_hades_merkle_paths (gstark_hades.h) with digest = 1.  That gather belongs to no hash family: it
+ * reads nothing but a node array in the heap layout, and keeps the name it was first exported with.
  *
  * These entry points are OPTIONAL on an implementation of the ABI (include/gstark.h lists the mandatory ones), like those of
  * gstark_hades.h: the HIP library exports them; a binding that does not find them computes on host integers

@@ -6,17 +6,11 @@
 // launch — and .merkleTree(values): the example's MerkleTree (nodes, root, prove, static verify) built by the device, with
 // proveMany(indexes) in one read-back.  `field` is a PrimeField of js/galois.js.  A field whose library lacks the entry points (they
 // are optional on an implementation of the ABI) makes the device members throw an Error saying so.
-const { Matrix, Vector } = require('./galois.js');
+const { Vector } = require('./galois.js');
+const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, verifyPath } = require('./field_tree.js');
 
-const registry = (typeof FinalizationRegistry !== 'undefined')
-    ? new FinalizationRegistry(({ lib, ctx, handle }) => { try { lib.call('gs_rescue_destroy', ctx, handle); } catch (e) { /* context gone */ } })
-    : null;
-
-function needDevice(field) {
-    if (!field.lib.has || !field.lib.has('gs_rescue_hash')) {
-        throw new Error(`the library of the field of ${field.modulus} elements has no gs_rescue_* entry points (include/gstark_rescue.h): Rescue hashes and trees are not computed on this device library`);
-    }
-}
+const registry = destroyRegistry('gs_rescue_destroy');
+const needDevice = field => needDeviceOf(field, 'rescue', 'Rescue');
 
 /** new Rescue(...) of utils.ts:33; invAlpha may be negative, as in the examples */
 function createRescue(field, alpha, invAlpha, registers, rounds, mds, constants) {
@@ -41,7 +35,7 @@ function createRescue(field, alpha, invAlpha, registers, rounds, mds, constants)
         while (state.length < m) state.push(0n);
         return state;
     };
-    let keys = null, handle = null;
+    let keys = null;
 
     const rescue = {
         field, alpha, invAlpha, invExponent, registers: m, rounds, mds: matrix,
@@ -93,32 +87,20 @@ function createRescue(field, alpha, invAlpha, registers, rounds, mds, constants)
             return rescue.modifiedSponge(inputs).hash[0];
         },
         /** the gs_rescue of this parameter set on the field's context (a BigInt): constants uploaded once, on first use */
-        handle() {
-            if (handle === null) {
-                needDevice(field);
-                const out = Buffer.alloc(8);
-                field.lib.call('gs_rescue_create', field.ctx, m, rounds, alpha, field.packLe([invExponent]), field.packLe([].concat(...matrix)),
-                    field.packLe([].concat(...rescue.keys)), out);
-                handle = out.readBigUInt64LE(0);
-                if (registry) registry.register(rescue, { lib: field.lib, ctx: field.ctx, handle });
-            }
-            return handle;
-        },
+        handle: lazyHandle(field, needDevice, registry, () => rescue, out =>
+            field.lib.call('gs_rescue_create', field.ctx, m, rounds, alpha, field.packLe([invExponent]), field.packLe([].concat(...matrix)),
+                field.packLe([].concat(...rescue.keys)), out)),
         /** one permutation per row of a device Matrix (or of rows of BigInts): a Matrix of rowCount x digest */
         hashMany(rows, digest = 1, modified = true, form = 0) {
             needDevice(field);
-            if (!(rows instanceof Matrix)) rows = field.newMatrixFrom(rows);
-            field._own(rows);
-            const out = new Matrix(field, rows.rowCount, digest);
-            field.lib.call('gs_rescue_hash', field.ctx, rescue.handle(), rows.ptr, rows.rowCount, rows.colCount, digest, modified ? 1 : 0, form, out.ptr);
-            return out;
+            return hashMany(field, 'gs_rescue_hash', rescue.handle(), rows, digest, modified ? 1 : 0, form);
         },
         merkleTree(values) { return new MerkleTree(values, rescue); },
     };
     return rescue;
 }
 
-class MerkleTree {      // utils.ts:232-273, built by the device
+class MerkleTree extends DeviceTree {      // utils.ts:232-273, built by the device
     constructor(values, rescue) {
         const field = rescue.field;
         if (!field || !rescue.handle) throw new Error('the hash must come from createRescue of js/rescue.js');
@@ -126,31 +108,12 @@ class MerkleTree {      // utils.ts:232-273, built by the device
         const src = Array.isArray(values) ? field.newVectorFrom(values) : values;
         if (!(src instanceof Vector)) throw new Error('the leaves are an array of BigInts or a Vector');
         field._own(src);
-        const n = src.length;
-        this.field = field; this.rescue = rescue; this.leafCount = n;
-        this.depth = Math.round(Math.log2(n));
-        this.deviceNodes = new Vector(field, 2 * n);
-        field.lib.call('gs_rescue_merkle', field.ctx, rescue.handle(), src.ptr, n, this.deviceNodes.ptr);
-    }
-    get nodes() { const values = this.deviceNodes.toValues(); values[0] = undefined; return values; }
-    get root() { return this.deviceNodes.getValue(1); }
-    prove(index) { return this.proveMany([index])[0]; }
-    /** prove(index) for every index (repeats allowed): one launch, one read-back */
-    proveMany(indexes) {
-        if (!indexes.length) return [];
-        const per = this.depth + 1, out = new Vector(this.field, indexes.length * per);
-        this.field.lib.call('gs_hades_merkle_paths', this.field.ctx, this.deviceNodes.ptr, this.leafCount, 1, indexes, indexes.length, out.ptr);
-        const values = out.toValues();
-        return indexes.map((_, k) => values.slice(k * per, (k + 1) * per));
+        super(field, rescue.handle(), 1, src, count => new Vector(field, count),
+            (handle, leaves, n, nodes) => field.lib.call('gs_rescue_merkle', field.ctx, handle, leaves.ptr, n, nodes.ptr));
+        this.rescue = rescue;
     }
     /** hash: a function of two values (rescue.hash2) */
-    static verify(root, index, proof, hash) {
-        let v = proof[0];
-        for (let level = 1; level < proof.length; level++) {
-            v = Math.floor(index / 2 ** (level - 1)) % 2 === 1 ? hash(proof[level], v) : hash(v, proof[level]);
-        }
-        return root === v;
-    }
+    static verify(root, index, proof, hash) { return verifyPath(root, index, proof, hash); }
 }
 
 module.exports = { createRescue, MerkleTree };

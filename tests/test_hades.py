@@ -9,7 +9,6 @@ import ctypes as C
 import json
 import os
 import random
-import shutil
 import subprocess
 import sys
 
@@ -23,27 +22,17 @@ from genstark_amd import _abi, lib128, lib224, poseidon
 from genstark_amd._abi import Backend, GstarkError
 from genstark_amd.field import PrimeField
 from genstark_amd.hades import HadesHash, HadesMerkleTree
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'gstark_hades.h')
-NODE = shutil.which('node')
-HAVE_HEADERS = os.path.exists('/usr/include/node/node_api.h')
-needs_node = pytest.mark.skipif(not (NODE and HAVE_HEADERS), reason='node or its headers are not in this image')
+from sponge_common import FLAVOURS, ROOT, check_header_is_plain_c, check_symbol_table, flavour_fixture, heap_nodes, input_rows, needs_node, run_js
 
 
 # ---- CPU tier: header and binding table -------------------------------------------------------------------------------------------
 def test_header_is_plain_c():
-    r = subprocess.run(['gcc', '-fsyntax-only', '-x', 'c', '-std=c99', '-Wall', '-Werror', HEADER], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c('hades')
 
 
 def test_symbol_table_matches_the_header():
-    header = open(HEADER).read()
     assert len(_abi.HADES_SYMBOLS) == 6
-    for name in _abi.HADES_SYMBOLS:
-        assert name + '(' in header, name
-    assert set(_abi.HADES_SYMBOLS).isdisjoint(_abi.EXPORTED_SYMBOLS) and set(_abi.HADES_SYMBOLS).isdisjoint(_abi.OPTIONAL_SYMBOLS)
-    assert 'gs_hades' not in open(os.path.join(ROOT, 'include', 'gstark.h')).read()
+    check_symbol_table('hades', _abi.HADES_SYMBOLS, (_abi.EXPORTED_SYMBOLS, _abi.OPTIONAL_SYMBOLS))
 
 
 def test_the_double_lacks_the_entries_and_loads(oracle_backend):
@@ -138,24 +127,13 @@ def test_bad_shapes_raise(oracle_backend):
 
 
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------------
-FLAVOURS = {'p128': None, 'p224': _abi.MODULUS_224, 'q64': _abi.MODULUS_64}
 COUNTS = (1, 63, 64, 65, 257, 1000)                   # the seams of a wave (64 lanes) and of a workgroup (256 threads)
 WIDTHS = (2, 3, 6, 8)
 ROUND_SHAPES = ((2, 0), (8, 1), (8, 55))
 ALPHAS = (3, 5, 17)
 
 
-@pytest.fixture(scope='module', params=list(FLAVOURS))
-def flavour(request):
-    be = Backend(device=0, modulus=FLAVOURS[request.param])
-    yield be
-    be.close()
-
-
-def input_rows(rng, p, count, arity):
-    """rows of `arity` inputs: 0, 1 and p - 1 in every position of the first rows, random elements after"""
-    special = [[v] * arity for v in (0, 1, p - 1)] + [[(0, 1, p - 1)[(j + s) % 3] for j in range(arity)] for s in range(3)]
-    return (special + [[rng.randrange(p) for _ in range(arity)] for _ in range(max(count - len(special), 0))])[:count]
+flavour = flavour_fixture()
 
 
 def check_counts(be, rng):
@@ -199,11 +177,7 @@ def test_permutations_of_every_shape(flavour):
 
 
 def host_tree(h, leaves, digest):
-    n = len(leaves)
-    nodes = [[0] * digest] * n + [list(leaf) for leaf in leaves]
-    for i in range(n - 1, 0, -1):
-        nodes[i] = h.hash(nodes[2 * i] + nodes[2 * i + 1])[:digest]
-    return nodes
+    return heap_nodes([list(leaf) for leaf in leaves], lambda left, right: h.hash(left + right)[:digest], [0] * digest)
 
 
 def check_trees(be, rng, sizes=None):
@@ -343,27 +317,16 @@ def js_expectations(path):
         json.dump(out, fh)
 
 
-def run_js(mode, env_extra, tmp_path):
-    subprocess.check_call(['bash', os.path.join(ROOT, 'napi', 'build.sh')], stdout=subprocess.DEVNULL)
-    want = tmp_path / 'want.json'
-    js_expectations(want)
-    r = subprocess.run(['timeout', '-k', '10', '240', NODE, os.path.join(ROOT, 'tests', 'js_hades.js'), mode, str(want)], cwd=ROOT,
-                       env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and f'js hades ({mode}) OK' in r.stdout, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
-
-
 @needs_node
 def test_js_on_a_library_without_the_entries(tmp_path):
     """createHash's function is host arithmetic and equals the Python host; the device members throw an Error that names what is missing"""
-    from conftest import _build_oracle
-    _build_oracle()
-    run_js('double', {'GSTARK_LIB_DIR': os.path.join(ROOT, 'oracle'), 'GSTARK_ALLOW_TEST_DOUBLE': '1'}, tmp_path)
+    run_js('hades', 'double', tmp_path, js_expectations)
 
 
 @needs_node
 @pytest.mark.gpu
 def test_js_on_hip(tmp_path):
-    run_js('hip', {}, tmp_path)
+    run_js('hades', 'hip', tmp_path, js_expectations)
 
 
 if __name__ == '__main__':

@@ -10,7 +10,6 @@ import ctypes as C
 import json
 import os
 import random
-import shutil
 import subprocess
 import sys
 
@@ -26,12 +25,8 @@ from genstark_amd.field import PrimeField
 from genstark_amd.hostfield import HostField
 from genstark_amd.rescue_hash import (RescueHash, RescueMerkleTree, rescue2x64, rescue4x128, rescue_merkle_inputs,
                                       rescue_merkle_proof_air)
+from sponge_common import FLAVOURS, ROOT, check_header_is_plain_c, check_symbol_table, flavour_fixture, heap_nodes, input_rows, needs_node, run_js
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'gstark_rescue.h')
-NODE = shutil.which('node')
-HAVE_HEADERS = os.path.exists('/usr/include/node/node_api.h')
-needs_node = pytest.mark.skipif(not (NODE and HAVE_HEADERS), reason='node or its headers are not in this image')
 OPTS = {'hashAlgorithm': 'blake2s256', 'extensionFactor': 16, 'exeQueryCount': 60, 'friQueryCount': 24}        # merkleProof.ts:43-49
 
 
@@ -45,18 +40,12 @@ def random_hash(f, rng, width, rounds, alpha=3, inv=None):
 
 # ---- CPU tier: header and binding table -------------------------------------------------------------------------------------------
 def test_header_is_plain_c():
-    r = subprocess.run(['gcc', '-fsyntax-only', '-x', 'c', '-std=c99', '-Wall', '-Werror', HEADER], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    check_header_is_plain_c('rescue')
 
 
 def test_symbol_table_matches_the_header():
-    header = open(HEADER).read()
     assert len(_abi.RESCUE_SYMBOLS) == 5 and len(_abi.HADES_SYMBOLS) == 6
-    for name in _abi.RESCUE_SYMBOLS:
-        assert name + '(' in header, name
-    for table in (_abi.EXPORTED_SYMBOLS, _abi.OPTIONAL_SYMBOLS, _abi.HADES_SYMBOLS):
-        assert set(_abi.RESCUE_SYMBOLS).isdisjoint(table)
-    assert 'gs_rescue' not in open(os.path.join(ROOT, 'include', 'gstark.h')).read()
+    check_symbol_table('rescue', _abi.RESCUE_SYMBOLS, (_abi.EXPORTED_SYMBOLS, _abi.OPTIONAL_SYMBOLS, _abi.HADES_SYMBOLS))
 
 
 def test_the_double_lacks_the_entries_and_loads(oracle_backend):
@@ -95,9 +84,7 @@ def test_hash2_equals_the_hash_air(oracle_backend):
 
 def check_tree(tree, leaves):
     h, n = tree.hash, len(leaves)
-    want = [None] * n + list(leaves)
-    for i in range(n - 1, 0, -1):
-        want[i] = h.hash2(want[2 * i], want[2 * i + 1])
+    want = heap_nodes(leaves, h.hash2, None)
     assert tree.nodes == want and tree.root == want[1]
     paths = tree.proveMany(list(range(n)))
     for i in range(n):
@@ -121,6 +108,23 @@ def test_trees_on_the_fallback(oracle_backend, n):
     check_tree(tree, leaves)
     if n == 4:                                       # leaves already on a device: the same tree
         assert RescueMerkleTree(h, f.newVectorFrom(leaves)).nodes == tree.nodes
+
+
+def test_the_shared_tree_base_keeps_the_two_faces_apart(oracle_backend):
+    """both trees over the same 8 leaves: each one's proveMany is its own prove, index by index, and each refuses under its own name"""
+    from genstark_amd.hades import HadesHash, HadesMerkleTree
+    f = PrimeField(backend=oracle_backend)
+    rng = random.Random(8)
+    leaves = [rng.randrange(f.modulus) for _ in range(8)]
+    for name, tree in (('RescueMerkleTree', RescueMerkleTree(random_hash(f, rng, 3, 2), leaves)), ('HadesMerkleTree', HadesMerkleTree(HadesHash(f, 3, 2, 1, 3), leaves, 1))):
+        paths = tree.proveMany(list(range(8)))
+        for i in range(8):
+            assert tree.prove(i) == paths[i] and paths[i][0] == leaves[i] and len(paths[i]) == 4 and all(isinstance(v, int) for v in paths[i])
+        for bad in (8, -1):
+            with pytest.raises(GstarkError, match=f'^{name}: an index is outside of the 8 leaves'):
+                tree.proveMany([0, bad])
+    with pytest.raises(GstarkError, match='^RescueMerkleTree: 0 leaves'):                # an n x 1 Matrix is leaves of the Hades face alone
+        RescueMerkleTree(random_hash(f, rng, 3, 2), f.newMatrixFrom([[v] for v in leaves]))
 
 
 def test_bad_shapes_raise(oracle_backend):
@@ -188,23 +192,12 @@ def test_merkle_statement_under_the_mirror_stark(oracle_backend):
 
 
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------------
-FLAVOURS = {'p128': None, 'q64': _abi.MODULUS_64, 'p224': _abi.MODULUS_224}
 WIDTHS = (2, 3, 4, 8)
 SEAM_COUNTS = (1, 7, 8, 9, 63, 64, 65, 257, 1000)        # the seams of a group of 8 lanes and of a wave; several workgroups
 DISTINCT = 997                                           # rows beyond this repeat the first ones: no longer host reference, other places
 
 
-@pytest.fixture(scope='module', params=list(FLAVOURS))
-def flavour(request):
-    be = Backend(device=0, modulus=FLAVOURS[request.param])
-    yield be
-    be.close()
-
-
-def input_rows(rng, p, count, arity):
-    """rows of `arity` inputs: 0, 1 and p - 1 in every position of the first rows, random elements after"""
-    special = [[v] * arity for v in (0, 1, p - 1)] + [[(0, 1, p - 1)[(j + s) % 3] for j in range(arity)] for s in range(3)]
-    return (special + [[rng.randrange(p) for _ in range(arity)] for _ in range(max(count - len(special), 0))])[:count]
+flavour = flavour_fixture('p128', 'q64', 'p224')
 
 
 def check_both_forms(h, rows, counts, sponges=(True, False), digests=(1, 2), forms=(0, 1, 2)):
@@ -280,11 +273,7 @@ def test_every_branch_of_the_exponent_schedule(flavour):
 
 
 def host_nodes(h, leaves):
-    n = len(leaves)
-    nodes = [0] * n + list(leaves)
-    for i in range(n - 1, 0, -1):
-        nodes[i] = h.hash2(nodes[2 * i], nodes[2 * i + 1])
-    return nodes
+    return heap_nodes(leaves, h.hash2, 0)
 
 
 def check_trees(be, rng, sizes=(2, 4, 64, 128, 256, 512, 1 << 11)):
@@ -419,27 +408,16 @@ def js_expectations(path):
         json.dump(out, fh)
 
 
-def run_js(mode, env_extra, tmp_path):
-    subprocess.check_call(['bash', os.path.join(ROOT, 'napi', 'build.sh')], stdout=subprocess.DEVNULL)
-    want = tmp_path / 'want.json'
-    js_expectations(want)
-    r = subprocess.run(['timeout', '-k', '10', '240', NODE, os.path.join(ROOT, 'tests', 'js_rescue.js'), mode, str(want)], cwd=ROOT,
-                       env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and f'js rescue ({mode}) OK' in r.stdout, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
-
-
 @needs_node
 def test_js_on_a_library_without_the_entries(tmp_path):
     """the host members equal the Python host; the device members throw an Error that names what is missing"""
-    from conftest import _build_oracle
-    _build_oracle()
-    run_js('double', {'GSTARK_LIB_DIR': os.path.join(ROOT, 'oracle'), 'GSTARK_ALLOW_TEST_DOUBLE': '1'}, tmp_path)
+    run_js('rescue', 'double', tmp_path, js_expectations)
 
 
 @needs_node
 @pytest.mark.gpu
 def test_js_on_hip(tmp_path):
-    run_js('hip', {}, tmp_path)
+    run_js('rescue', 'hip', tmp_path, js_expectations)
 
 
 if __name__ == '__main__':

@@ -15,20 +15,19 @@ Times are host clock around `reps` back-to-back launches that end in one gs_sync
 least --window seconds long.  Needs the GPU: there is no fallback."""
 import argparse
 import ctypes as C
-import glob
-import json
 import os
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 from genstark_amd import _abi, lib128, lib224          # noqa: E402
 from genstark_amd._abi import Backend                  # noqa: E402
 from genstark_amd.field import Matrix, PrimeField      # noqa: E402
+from sponge_bench import LANES, SIMDS, product_cost, timed      # noqa: E402
 
-SIMDS, LANES = 1024, 64
 # waves per SIMD of the kernels timed here, from -Rpass-analysis=kernel-resource-usage (DESIGN.md 3.8)
 OCCUPANCY = {('p128', 6): 4, ('p224', 3): 3}
 
@@ -43,31 +42,6 @@ def iter_bits(e):
     while e > 1:
         yield e
         e >>= 1
-
-
-def timed(be, launch, window):
-    launch()
-    be.sync()
-    t0 = time.perf_counter()
-    launch()
-    be.sync()
-    once = max(time.perf_counter() - t0, 1e-6)
-    reps = max(3, int(window / once) + 1)
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        launch()
-    be.sync()
-    return (time.perf_counter() - t0) / reps, reps
-
-
-def product_cost(detail_path):
-    """ns per wave-wide 128-bit product at 1 .. 4 waves per SIMD, and where it came from"""
-    paths = [detail_path] if os.path.exists(detail_path) else sorted(glob.glob(os.path.join(ROOT, 'profiles', '*bench_detail.json')))[-1:]
-    for path in paths:
-        table = json.load(open(path)).get('roofline', {}).get('second_roof', {}).get('measured_ns_per_wave_at_1_2_3_4_waves_per_simd', {})
-        if 'canonical_limb_fe_mul_for_reference' in table:
-            return table['canonical_limb_fe_mul_for_reference'], os.path.relpath(path, ROOT)
-    return None, None
 
 
 def main():

@@ -32,7 +32,7 @@ from genstark_amd._abi import Backend, MODULUS_128                        # noqa
 from genstark_amd.field import Matrix, PrimeField, Vector                 # noqa: E402
 from genstark_amd.hostfield import HostField                              # noqa: E402
 from genstark_amd.rescue_hash import RescueMerkleTree, rescue4x128        # noqa: E402
-from hades_bench import LANES, SIMDS, product_cost, timed                 # noqa: E402
+from sponge_bench import LANES, SIMDS, product_cost, timed     # noqa: E402
 
 CSRC = os.path.join(ROOT, 'genstark_amd', 'csrc')
 CANONICAL_LIB = os.path.join(CSRC, 'libgstark_hip_rescue_canonical.so')
