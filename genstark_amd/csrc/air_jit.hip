@@ -32,7 +32,7 @@
 #include <mutex>
 
 #include "common.h"
-#include "host_sha256.h"
+#include "host_hash.h"
 
 enum { J_LOADC = 0, J_LOADR = 1, J_LOADN = 2, J_LOADS = 3, J_ADDV = 4, J_SUBV = 5, J_MULV = 6, J_POW = 7, J_POWC = 8, J_OUT = 9 };
 

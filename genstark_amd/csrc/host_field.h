@@ -1,16 +1,43 @@
-// host_field.h — GF(p) arithmetic on native 64-bit limbs for the few HOST-side pieces of the library:
-// the serial MiMC recurrence (air_mimc.hip) and O(n^2) Lagrange interpolation of <= a few hundred points
-// (small.hip).  Same modulus and canonical representation as gf128.h.
+// host_field.h — GF(p) arithmetic on native 64-bit limbs for everything the HOST side computes in the field: the serial MiMC
+// recurrence (air_mimc.hip), the host interpreter of AIR programs (air_vm.hip, through host_pow.h), Lagrange interpolation and
+// evaluation of a few thousand points (small.hip), and the scalars of the native drivers and the verifier (prover.cc, prover_dist.h,
+// verifier.h); host_poly.h builds its polynomial helpers on it.  Same modulus and canonical representation as the device header of
+// the build flavour (gf128.h, gf_small.h, gf_wide.h).
+//
+// ONE interface in every flavour (this file: the 128-bit field; host_field_small.h: GS_SMALL_Q; host_field_wide.h: GS_WIDE_BITS), so
+// that a consumer needs no flavour test of its own:
+//   hfe                                  an element: constructible from a uint64_t, comparable with == / != (CANONICAL values only)
+//   HF_ELT                               its size in bytes on the ABI and in a proof (16 or 32); hf_load / hf_store move that many
+//   hf_add hf_sub hf_mul hf_pow hf_inv   canonical in, canonical out (0^-1 = 0, galois' convention); hf_is_zero
+//   hf_mul_weak hf_add_weak hf_canon     the chain trio: ANY representative in, any representative out, and hf_canon ends a chain with
+//                                        the canonical value.  Only the 128-bit field has a weak form (below); in the other flavours the
+//                                        two operations are the canonical ones and hf_canon is the identity.
+//   hf_from_digest                       a 256-bit big-endian integer (a digest) mod p
+//   hf_modulus_bytes                     p as HF_ELT little-endian bytes
+//   hf_mimc_step* hf_mimc_out            the MiMC recurrence (air_mimc.hip)
 #pragma once
+#if defined(GS_SMALL_Q) || defined(GS_WIDE_BITS)
 #if defined(GS_SMALL_Q)
 #include "host_field_small.h"
-#elif defined(GS_WIDE_BITS)
+#else
 #include "host_field_wide.h"
+#endif
+// what the two share: no weak form, and a digest folded in byte by byte
+static inline hfe hf_mul_weak(hfe a, hfe b) { return hf_mul(a, b); }
+static inline hfe hf_add_weak(hfe a, hfe b) { return hf_add(a, b); }
+static inline hfe hf_canon(hfe x) { return x; }
+static inline hfe hf_from_digest(const uint8_t d[32]) {
+    hfe x = 0;
+    const hfe b = 256;
+    for (int i = 0; i < 32; i++) x = hf_add(hf_mul(x, b), (hfe)(uint64_t)d[i]);
+    return x;
+}
 #else
 #include <stdint.h>
 #include <string.h>
 
 typedef unsigned __int128 hfe;
+#define HF_ELT 16
 
 static inline hfe hf_p() { return ((hfe)0xFFFFFFFFFFFFFFFFull << 64) | 0xFFFFFFF700000001ull; }
 static const hfe HF_C = (hfe)0x8FFFFFFFFull;  // 2^128 mod p
@@ -99,9 +126,6 @@ static inline hfe hf_canon(hfe x) {
     while (x >= hf_p()) x -= hf_p();
     return x;
 }
-// products inside a long chain whose end is canonicalised once (host_pow in air_vm.hip)
-#define HF_CHAIN_MUL hf_mul_weak
-#define HF_CHAIN_END hf_canon
 // sum of two weak values (any 128-bit representatives), weak again: a wrap past 2^128 comes back as + C (2^128 == C mod p), branch-free.
 // The wrapped sum can be as large as 2^128 - 2, so adding C may wrap ONCE more (when both operands are within ~2^36 of 2^128); that
 // second wrap leaves a value below C and is paid back the same way — a third is impossible.
@@ -110,7 +134,6 @@ static inline hfe hf_add_weak(hfe a, hfe b) {
     const hfe t = s + (((hfe)0 - (hfe)(s < a)) & HF_C);
     return t + (((hfe)0 - (hfe)(t < s)) & HF_C);
 }
-#define HF_CHAIN_ADD hf_add_weak
 static inline hfe hf_add(hfe a, hfe b) {
     hfe s = a + b;
     if (s < a || s >= hf_p()) s -= hf_p();
@@ -130,6 +153,13 @@ static inline hfe hf_inv(hfe a) { return a ? hf_pow(a, hf_p() - 2) : 0; }
 static inline bool hf_is_zero(hfe a) { return a == 0; }
 static inline hfe hf_load(const uint8_t *b) { hfe v; memcpy(&v, b, 16); return v; }
 static inline void hf_store(uint8_t *b, hfe v) { memcpy(b, &v, 16); }
+static inline hfe hf_from_digest(const uint8_t d[32]) {
+    hfe hi = 0, lo = 0;
+    for (int i = 0; i < 16; i++) hi = (hi << 8) | d[i];
+    for (int i = 16; i < 32; i++) lo = (lo << 8) | d[i];
+    return hf_reduce(hi, lo);
+}
+static inline void hf_modulus_bytes(uint8_t *out) { hf_store(out, hf_p()); }
 // x^3 + k in one go, weak in and weak out (any 128-bit representatives; k < 2^128): hf_cube_weak with k's two limbs joining the limb sums
 // of the first fold.  A separate "+ k" after the cube wraps past 2^128 every other step (k is a uniform residue) — a select or a
 // mispredicted branch on the chain — and a canonical chain adds its compare-and-subtract to every step; here the constant costs no
@@ -242,4 +272,4 @@ static inline hfe hf_mimc_step(hfe x, hfe k) {
     if (sum < y) sum += HF_C;                          // wrapped past 2^128: +2^128 == +C (the wrapped value is small)
     return hf_canon(sum);
 }
-#endif  // GS_SMALL_Q
+#endif  // the 128-bit field

@@ -1,5 +1,6 @@
-// host_field_wide.h — the host-side GF(p) helpers of host_field.h for the 256- / 224-bit build flavours (see gf_wide.h):
-// same names; an element wraps the device header's `fe` (its functions are host + device) and converts from small integers.
+// host_field_wide.h — the host-side GF(p) helpers of host_field.h for the 256- / 224-bit build flavours (see gf_wide.h, which the
+// includer brings in first): the same interface (host_field.h lists it, and adds the chain trio and hf_from_digest); an element wraps
+// the device header's `fe` (its functions are host + device), converts from small integers and compares with == / !=.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -9,6 +10,9 @@ struct hfe {
     hfe() : v(fe_zero()) {}
     hfe(uint64_t x) : v(fe_make((uint32_t)x, (uint32_t)(x >> 32), 0, 0)) {}
 };
+#define HF_ELT 32
+static inline bool operator==(const hfe &a, const hfe &b) { return fe_eq(a.v, b.v); }
+static inline bool operator!=(const hfe &a, const hfe &b) { return !fe_eq(a.v, b.v); }
 
 static inline hfe hf_wrap(const fe &v) { hfe r; r.v = v; return r; }
 static inline hfe hf_add(hfe a, hfe b) { return hf_wrap(fe_add(a.v, b.v)); }
@@ -139,3 +143,6 @@ static inline hfe hf_mimc_out(hfe x) { return x; }
 static inline bool hf_is_zero(hfe a) { return fe_is_zero(a.v); }
 static inline hfe hf_load(const uint8_t *b) { hfe r; memcpy(&r.v, b, sizeof(fe)); return r; }
 static inline void hf_store(uint8_t *b, hfe x) { memcpy(b, &x.v, sizeof(fe)); }
+static inline void hf_modulus_bytes(uint8_t *out) {
+    for (int i = 0; i < GF_LIMBS; i++) { const uint32_t w = gf_p_limb(i); memcpy(out + 4 * i, &w, 4); }
+}

@@ -1,9 +1,12 @@
-// host_sha256.h — SHA-256 on the HOST for the few Fiat-Shamir hashes the host side computes itself (query positions,
-// random coefficients: QueryIndexGenerator.ts:39-67, galois prng), plus the reference's bigint -> bytes quirk.
+// host_hash.h — the hashes the HOST side computes itself: SHA-256 for the Fiat-Shamir steps (query positions, random coefficients:
+// QueryIndexGenerator.ts:39-67, galois prng) and the code-object names of air_jit.hip, BLAKE2s-256 beside it for the native verifier's
+// Merkle checks (verifier.h: host_digest picks by gs_hash_alg), plus the reference's bigint -> bytes quirk.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "../../include/gstark.h"
 
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -89,6 +92,49 @@ static inline void host_sha256(const uint8_t *msg, size_t len, uint8_t out[32]) 
     for (int i = 0; i < 8; i++) { out[4 * i] = (uint8_t)(h[i] >> 24); out[4 * i + 1] = (uint8_t)(h[i] >> 16); out[4 * i + 2] = (uint8_t)(h[i] >> 8); out[4 * i + 3] = (uint8_t)h[i]; }
 }
 
+// BLAKE2s-256, unkeyed (RFC 7693) — the merkle package's 'blake2s256' (SURVEY appendix A.7).  A verification is ~5 000
+// compressions: the state lives in sixteen locals and the ten rounds are written out (the message schedule as compile-time indices).
+#define B2S_ROTR(x, r) (((x) >> (r)) | ((x) << (32 - (r))))
+#define B2S_G(a, b, c, d, x, y)                                                                       \
+    a = a + b + (x); d = B2S_ROTR(d ^ a, 16); c = c + d; b = B2S_ROTR(b ^ c, 12);                        \
+    a = a + b + (y); d = B2S_ROTR(d ^ a, 8); c = c + d; b = B2S_ROTR(b ^ c, 7);
+#define B2S_ROUND(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)             \
+    B2S_G(v0, v4, v8, v12, m[s0], m[s1]) B2S_G(v1, v5, v9, v13, m[s2], m[s3]) B2S_G(v2, v6, v10, v14, m[s4], m[s5]) B2S_G(v3, v7, v11, v15, m[s6], m[s7]) \
+    B2S_G(v0, v5, v10, v15, m[s8], m[s9]) B2S_G(v1, v6, v11, v12, m[s10], m[s11]) B2S_G(v2, v7, v8, v13, m[s12], m[s13]) B2S_G(v3, v4, v9, v14, m[s14], m[s15])
+static inline void host_blake2s_compress(uint32_t h[8], const uint8_t b[64], uint64_t t, bool last) {
+    uint32_t m[16];
+    memcpy(m, b, 64);                          // little-endian host
+    uint32_t v0 = h[0], v1 = h[1], v2 = h[2], v3 = h[3], v4 = h[4], v5 = h[5], v6 = h[6], v7 = h[7];
+    uint32_t v8 = 0x6A09E667u, v9 = 0xBB67AE85u, v10 = 0x3C6EF372u, v11 = 0xA54FF53Au;
+    uint32_t v12 = 0x510E527Fu ^ (uint32_t)t, v13 = 0x9B05688Cu ^ (uint32_t)(t >> 32), v14 = last ? ~0x1F83D9ABu : 0x1F83D9ABu, v15 = 0x5BE0CD19u;
+    B2S_ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
+    B2S_ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
+    B2S_ROUND(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
+    B2S_ROUND(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
+    B2S_ROUND(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
+    B2S_ROUND(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
+    B2S_ROUND(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
+    B2S_ROUND(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
+    B2S_ROUND(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
+    B2S_ROUND(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
+    h[0] ^= v0 ^ v8; h[1] ^= v1 ^ v9; h[2] ^= v2 ^ v10; h[3] ^= v3 ^ v11; h[4] ^= v4 ^ v12; h[5] ^= v5 ^ v13; h[6] ^= v6 ^ v14; h[7] ^= v7 ^ v15;
+}
+#undef B2S_ROUND
+#undef B2S_G
+#undef B2S_ROTR
+static inline void host_blake2s(const uint8_t *msg, size_t len, uint8_t out[32]) {
+    uint32_t h[8] = {0x6A09E667u ^ 0x01010020u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au, 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
+    const size_t nblocks = len ? (len + 63) / 64 : 1;
+    for (size_t blk = 0; blk + 1 < nblocks; blk++) host_blake2s_compress(h, msg + 64 * blk, (uint64_t)(blk + 1) * 64, false);
+    uint8_t b[64] = {0};
+    const size_t off = (nblocks - 1) * 64;
+    memcpy(b, msg + off, len - off);
+    host_blake2s_compress(h, b, len, true);
+    memcpy(out, h, 32);                        // little-endian host
+}
+static inline void host_digest(int alg, const uint8_t *msg, size_t len, uint8_t out[32]) {
+    if (alg == GS_HASH_SHA256) host_sha256(msg, len, out); else host_blake2s(msg, len, out);
+}
 
 // Buffer.from(value.toString(16), 'hex') for a big-endian value of n bytes: no leading zeros, an odd number of hex digits
 // loses the LAST nibble (QueryIndexGenerator.ts:61-67).  Returns the byte count written to out (<= n).

@@ -33,7 +33,8 @@
 #include "gf_wide.h"
 #endif
 #include "host_field.h"
-#include "host_sha256.h"
+#include "host_poly.h"
+#include "host_hash.h"
 
 namespace {
 
@@ -80,13 +81,7 @@ struct Fail {
 }
 
 typedef hfe F;
-#if defined(GS_WIDE_BITS)
-const uint64_t ELEM = sizeof(fe);               // 32: the 256- / 224-bit fields
-inline bool operator==(const F &a, const F &b) { return fe_eq(a.v, b.v); }
-inline bool operator!=(const F &a, const F &b) { return !fe_eq(a.v, b.v); }
-#else
-const uint64_t ELEM = 16;
-#endif
+const uint64_t ELEM = HF_ELT;                   // 16, or 32 in the 256- / 224-bit fields
 const uint64_t DIGEST = 32, MAX_ARRAY = 256;
 const uint64_t WORD = 16, EW = ELEM / WORD;     // gs_gather_words / gs_defer_* move 16-byte words
 static_assert(ELEM <= GS_PROVER_ELT_MAX, "element wider than the job's scalar fields");
@@ -128,25 +123,12 @@ struct Enc {
 Enc enc(F v) { Enc e; hf_store(e.b, v); return e; }
 
 // ---- galois prng (genstark_amd/field.py: prng — restated) and the index generator -----------------
-F digest_mod_p(const uint8_t d[32]) {          // 256-bit big-endian integer mod p
-#if !defined(GS_WIDE_BITS) && !defined(GS_SMALL_Q)
-    F hi = 0, lo = 0;
-    for (int i = 0; i < 16; i++) hi = (hi << 8) | d[i];
-    for (int i = 16; i < 32; i++) lo = (lo << 8) | d[i];
-    return hf_reduce(hi, lo);
-#else
-    F x = 0;                                    // byte-wise Horner: the same code for every other modulus
-    const F b = 256;
-    for (int i = 0; i < 32; i++) x = hf_add(hf_mul(x, b), (F)(uint64_t)d[i]);
-    return x;
-#endif
-}
 std::vector<F> prng_many(const Bytes &seed, size_t count) {
     std::vector<F> out(count);
     uint8_t st[32], msg[32];
     host_sha256(seed.data(), seed.size(), st);
     for (size_t i = 0; i < count; i++) {
-        out[i] = digest_mod_p(st);
+        out[i] = hf_from_digest(st);
         int n = host_bigint_bytes(st, 32, msg);
         host_sha256(msg, (size_t)n, st);
     }
@@ -155,7 +137,7 @@ std::vector<F> prng_many(const Bytes &seed, size_t count) {
 F prng_one(const Bytes &seed) {
     uint8_t st[32];
     host_sha256(seed.data(), seed.size(), st);
-    return digest_mod_p(st);
+    return hf_from_digest(st);
 }
 std::vector<uint64_t> query_indexes(const Bytes &seed, uint32_t count, uint64_t max, uint32_t exclude) {
     uint64_t max_count = exclude ? max - max / exclude : max;
@@ -490,11 +472,7 @@ static int bind_api(Api &api, void *dl_handle) {
     // process, like the library's
     { uint32_t pl[GF_LIMBS]; memcpy(pl, m, sizeof pl); if (gf_rt_configure(pl)) return GS_ERR_UNSUPPORTED; }
 #endif
-#if defined(GS_WIDE_BITS)
-    for (int i = 0; i < GF_LIMBS; i++) { const uint32_t w = gf_p_limb(i); memcpy(want + 4 * i, &w, 4); }
-#else
-    { const hfe pp = hf_p(); memcpy(want, &pp, 16); }
-#endif
+    hf_modulus_bytes(want);
     return memcmp(m, want, ELEM) ? GS_ERR_UNSUPPORTED : GS_OK;
 }
 int gs_prover_bind(void *dl_handle) {
@@ -652,26 +630,8 @@ static bool remainder_is_low_degree(const std::vector<F> &remainder, uint64_t E,
     if (!m || m == positions.size()) return true;
     if (method == 1 && E && len >= E && len % E == 0 && !(len & (len - 1))) {
         const uint64_t B = len / E;
-        std::vector<F> g(len), w(len / 2 ? len / 2 : 1);
-        int lg = 0;
-        while ((1ull << lg) < len) lg++;
-        for (uint64_t i = 0; i < len; i++) {               // bit-reversed input, decimation in time
-            uint64_t r = 0;
-            for (int b = 0; b < lg; b++) r |= ((i >> b) & 1) << (lg - 1 - b);
-            g[r] = remainder[i];
-        }
-        const F inv = hf_pow(rou, (hfe)(len - 1));          // rou^-1
-        F cur = 1;
-        for (uint64_t i = 0; i < len / 2; i++) { w[i] = cur; cur = hf_mul(cur, inv); }
-        for (uint64_t half = 1; half < len; half <<= 1)
-            for (uint64_t base = 0; base < len; base += 2 * half)
-                for (uint64_t j = 0; j < half; j++) {
-                    const F t = hf_mul(g[base + half + j], w[j * (len / (2 * half))]);
-                    const F u = g[base + j];
-                    g[base + j] = hf_add(u, t);
-                    g[base + half + j] = hf_sub(u, t);
-                }
-        // (unscaled: the predicate compares coefficients with each other)
+        std::vector<F> g(remainder);
+        host_transform(g, hf_pow(rou, (hfe)(len - 1)));     // with rou^-1; unscaled: the predicate compares (canonical) coefficients with each other
         for (uint64_t k = m; k + B < len; k++)
             if (g[k] != g[k + B]) return false;
         return true;
@@ -766,14 +726,7 @@ struct Plan {
 
     // the product of (x - x_i) over a register's assertions (BoundaryConstraints.ts:24-30)
     std::vector<F> zero_poly(const Reg &r) const {
-        std::vector<F> zp{(F)1};
-        for (F xi : r.xs) {
-            std::vector<F> nz(zp.size() + 1, (F)0);
-            const F nx = hf_sub(0, xi);
-            for (size_t k = 0; k < zp.size(); k++) { nz[k] = hf_add(nz[k], hf_mul(zp[k], nx)); nz[k + 1] = hf_add(nz[k + 1], zp[k]); }
-            zp.swap(nz);
-        }
-        return zp;
+        return host_linear_product(r.xs);
     }
     // the asserted registers as rows of `width` (the most assertions on one register) for the boundary kernels: where each assertion's
     // point lies, in units of the domain's generator (step * unit), the count per row and — with_interpolants — each row's interpolant

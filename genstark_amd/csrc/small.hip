@@ -8,34 +8,24 @@
 
 #include "common.h"
 #include "host_field.h"
-#include "host_sha256.h"
-#ifndef HF_CHAIN_MUL          // flavours without a weak form: the canonical operations
-#define HF_CHAIN_MUL hf_mul
-#define HF_CHAIN_END(x) (x)
-#endif
-#ifndef HF_CHAIN_ADD
-#define HF_CHAIN_ADD hf_add
-#endif
+#include "host_poly.h"
+#include "host_hash.h"
 
 extern "C" {
 
 int gs_small_interpolate(const uint8_t *xs_host, const uint8_t *ys_host, uint32_t n, uint8_t *coeffs_out) {
     if (!xs_host || !ys_host || !coeffs_out || n == 0 || n > 4096) return GS_ERR_ARG;
-    std::vector<hfe> x(n), y(n), master(n + 1, 0), out(n, 0);
+    std::vector<hfe> x(n), y(n), out(n, 0);
     for (uint32_t i = 0; i < n; i++) { x[i] = hf_load(xs_host + GS_ELT * i); y[i] = hf_load(ys_host + GS_ELT * i); }
-    // The three O(n^2) loops below run on WEAK values (any 128-bit representative: HF_CHAIN_MUL / HF_CHAIN_ADD, no compare-and-subtract
-    // per operation) and are canonicalised once at the end; independent chains are interleaved four at a time (a dependent product is
-    // ~15 ns of latency, an independent one ~4 ns of issue).  112 points (the remainder of a degree-6 AIR): 0.70 -> 0.19 ms, the 128 evaluations after it 0.23 -> 0.05 ms.
+    // The O(n^2) loops below and in host_linear_product run on WEAK values (any 128-bit representative: hf_mul_weak / hf_add_weak, no
+    // compare-and-subtract per operation) and are canonicalised once at the end; independent chains are interleaved four at a time (a
+    // dependent product is ~15 ns of latency, an independent one ~4 ns of issue).  112 points (the remainder of a degree-6 AIR):
+    // 0.70 -> 0.19 ms, the 128 evaluations after it 0.23 -> 0.05 ms.
     // master polynomial M(X) = prod (X - x_i)
-    master[0] = 1;
-    for (uint32_t i = 0; i < n; i++) {
-        hfe nx = hf_sub(0, x[i]);
-        for (uint32_t d = i + 1; d >= 1; d--) master[d] = HF_CHAIN_ADD(master[d - 1], HF_CHAIN_MUL(master[d], nx));
-        master[0] = HF_CHAIN_MUL(master[0], nx);
-    }
-    // Lagrange denominators q_j(x_j) = M'(x_j), all inverted with ONE field inversion (Montgomery's trick)
+    const std::vector<hfe> master = host_linear_product(x);
+    // Lagrange denominators q_j(x_j) = M'(x_j), all inverted with ONE field inversion (Montgomery's trick: host_batch_invert)
     const bool keep = n <= 512;                                // keep the n quotients (n coefficients each: 4 MB at most) or recompute them
-    std::vector<hfe> den(n), pre(n), qs(keep ? (size_t)n * n : n);
+    std::vector<hfe> den(n), qs(keep ? (size_t)n * n : n);
     // q_j = M / (X - x_j) by synthetic division, evaluated at x_j on the fly (Horner): four j's side by side
     for (uint32_t j0 = 0; j0 < n; j0 += 4) {
         const uint32_t w = n - j0 < 4 ? n - j0 : 4;
@@ -43,32 +33,28 @@ int gs_small_interpolate(const uint8_t *xs_host, const uint8_t *ys_host, uint32_
         for (uint32_t u = 0; u < 4; u++) xj[u] = x[j0 + (u < w ? u : 0)];
         for (uint32_t d = n; d >= 1; d--) {
             for (uint32_t u = 0; u < 4; u++) {
-                carry[u] = HF_CHAIN_ADD(master[d], HF_CHAIN_MUL(carry[u], xj[u]));
-                dj[u] = HF_CHAIN_ADD(HF_CHAIN_MUL(dj[u], xj[u]), carry[u]);
+                carry[u] = hf_add_weak(master[d], hf_mul_weak(carry[u], xj[u]));
+                dj[u] = hf_add_weak(hf_mul_weak(dj[u], xj[u]), carry[u]);
             }
             if (keep)
                 for (uint32_t u = 0; u < w; u++) qs[(size_t)(j0 + u) * n + d - 1] = carry[u];
         }
-        for (uint32_t u = 0; u < w; u++) den[j0 + u] = HF_CHAIN_END(dj[u]);
+        for (uint32_t u = 0; u < w; u++) den[j0 + u] = hf_canon(dj[u]);
     }
-    hfe acc = 1;
-    for (uint32_t j = 0; j < n; j++) { pre[j] = acc; if (!hf_is_zero(den[j])) acc = hf_mul(acc, den[j]); }
-    hfe inv_all = hf_inv(acc);
+    host_batch_invert(den);                       // (a repeated x makes its denominator zero: 0^-1 = 0)
     for (uint32_t j = n; j-- > 0;) {
-        hfe inv_j = 0;                            // a repeated x makes its denominator zero: 0^-1 = 0, as before
-        if (!hf_is_zero(den[j])) { inv_j = hf_mul(inv_all, pre[j]); inv_all = hf_mul(inv_all, den[j]); }
-        const hfe sc = hf_mul(y[j], inv_j);
+        const hfe sc = hf_mul(y[j], den[j]);
         if (!keep) {
             hfe carry = 0;
             for (uint32_t d = n; d >= 1; d--) {
-                carry = HF_CHAIN_ADD(master[d], HF_CHAIN_MUL(carry, x[j]));
+                carry = hf_add_weak(master[d], hf_mul_weak(carry, x[j]));
                 qs[d - 1] = carry;
             }
         }
         const hfe *qj = keep ? &qs[(size_t)j * n] : qs.data();
-        for (uint32_t d = 0; d < n; d++) out[d] = HF_CHAIN_ADD(out[d], HF_CHAIN_MUL(qj[d], sc));
+        for (uint32_t d = 0; d < n; d++) out[d] = hf_add_weak(out[d], hf_mul_weak(qj[d], sc));
     }
-    for (uint32_t d = 0; d < n; d++) out[d] = HF_CHAIN_END(out[d]);
+    for (uint32_t d = 0; d < n; d++) out[d] = hf_canon(out[d]);
     for (uint32_t d = 0; d < n; d++) hf_store(coeffs_out + GS_ELT * d, out[d]);
     return GS_OK;
 }
@@ -82,8 +68,8 @@ int gs_small_eval_poly(const uint8_t *poly_host, uint32_t len, const uint8_t *xs
         hfe x[4], acc[4] = {0, 0, 0, 0};
         for (uint32_t u = 0; u < 4; u++) x[u] = hf_load(xs_host + GS_ELT * (i0 + (u < w ? u : 0)));
         for (uint32_t k = len; k-- > 0;)
-            for (uint32_t u = 0; u < 4; u++) acc[u] = HF_CHAIN_ADD(HF_CHAIN_MUL(acc[u], x[u]), p[k]);
-        for (uint32_t u = 0; u < w; u++) hf_store(out_host + GS_ELT * (i0 + u), HF_CHAIN_END(acc[u]));
+            for (uint32_t u = 0; u < 4; u++) acc[u] = hf_add_weak(hf_mul_weak(acc[u], x[u]), p[k]);
+        for (uint32_t u = 0; u < w; u++) hf_store(out_host + GS_ELT * (i0 + u), hf_canon(acc[u]));
     }
     return GS_OK;
 }
@@ -186,25 +172,9 @@ extern "C" int gs_pseudorandom_indexes(const uint8_t *seed, uint32_t seed_len, u
         msg[0] = 0;
         for (int k = 31; k >= 0; k--) { uint64_t t = (uint64_t)st[k] + (carry & 0xFF); msg[k + 1] = (uint8_t)t; carry = (carry >> 8) + (t >> 8); }
         msg[0] = (uint8_t)carry;
-        /* hex digits without leading zeros; an odd count drops the last nibble: bytes = (v >> 4) then */
-        int lead = 0;
-        while (lead < 33 && msg[lead] == 0) lead++;
-        int nhex = lead == 33 ? 0 : (33 - lead) * 2 - ((msg[lead] >> 4) == 0 ? 1 : 0);
+        /* Buffer.from(v.toString(16), 'hex'): no leading zeros, an odd digit count drops the last nibble */
         uint8_t buf[33];
-        int nbytes = nhex / 2;
-        if (nhex & 1) {                               /* shift right by one nibble */
-            for (int k = 0; k < nbytes; k++) {
-                /* byte k of the result = nibbles 2k, 2k+1 of the hex string */
-                int hi_n = 2 * k, lo_n = 2 * k + 1;   /* nibble index from the most significant nibble of the string */
-                int first = lead * 2 + 1;             /* string starts at the low nibble of msg[lead] */
-                int a = first + hi_n, b = first + lo_n;
-                uint8_t na = (a & 1) ? (msg[a >> 1] & 15) : (msg[a >> 1] >> 4);
-                uint8_t nb = (b & 1) ? (msg[b >> 1] & 15) : (msg[b >> 1] >> 4);
-                buf[k] = (uint8_t)((na << 4) | nb);
-            }
-        } else {
-            for (int k = 0; k < nbytes; k++) buf[k] = msg[lead + k];
-        }
+        const int nbytes = host_bigint_bytes(msg, 33, buf);
         SHA256(buf, (size_t)nbytes, dg);
         /* index = dg (big-endian 256-bit) mod max */
         uint64_t index;

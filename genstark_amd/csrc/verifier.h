@@ -1,59 +1,16 @@
 // verifier.h — Stark.verify() (lib/Stark.ts:167-248) and LowDegreeProver.verify (lib/components/LowDegreeProver.ts:70-172) as
-// native host code (included once, by prover.cc: it shares the driver's scalar helpers, prng and index generator).
+// native host code (included once, by prover.cc: it shares the driver's statement plan, prng and index generator).
 //
 // CPU-side by design, like the reference's verifier: a proof is a few hundred field elements and a few thousand digests, there is
 // nothing for a GPU to do.  Input: the statement as a gs_prover_job (the fields a verifier needs: sizes, query counts, hash,
 // root of unity, assertions, and of the AIR its kind, register counts, constraint degrees and — kind 0 — the round constants or —
 // kind 1 — the constraint evaluator program with its constants and the PUBLIC static registers' values) + the serialized proof.
 // Every check of the reference is made, in its order, with its messages; what the reference computes on BigInt / wasm runs here on
-// the build flavour's host arithmetic (host_field*.h).  Hashing: host SHA-256 (SHA-NI when present) and a portable BLAKE2s.
+// the build flavour's host arithmetic (host_field.h) through the shared polynomial helpers (host_poly.h: transform, batch inversion,
+// product of linear factors, Horner).  Hashing: host_hash.h (SHA-256, with SHA-NI when present, and a portable BLAKE2s).
 #pragma once
 
 namespace {
-
-// ---- BLAKE2s-256, unkeyed (RFC 7693) — the merkle package's 'blake2s256' (SURVEY appendix A.7).  A verification is ~5 000
-// compressions: the state lives in sixteen locals and the ten rounds are written out (the message schedule as compile-time indices).
-#define B2S_ROTR(x, r) (((x) >> (r)) | ((x) << (32 - (r))))
-#define B2S_G(a, b, c, d, x, y)                                                                       \
-    a = a + b + (x); d = B2S_ROTR(d ^ a, 16); c = c + d; b = B2S_ROTR(b ^ c, 12);                        \
-    a = a + b + (y); d = B2S_ROTR(d ^ a, 8); c = c + d; b = B2S_ROTR(b ^ c, 7);
-#define B2S_ROUND(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)             \
-    B2S_G(v0, v4, v8, v12, m[s0], m[s1]) B2S_G(v1, v5, v9, v13, m[s2], m[s3]) B2S_G(v2, v6, v10, v14, m[s4], m[s5]) B2S_G(v3, v7, v11, v15, m[s6], m[s7]) \
-    B2S_G(v0, v5, v10, v15, m[s8], m[s9]) B2S_G(v1, v6, v11, v12, m[s10], m[s11]) B2S_G(v2, v7, v8, v13, m[s12], m[s13]) B2S_G(v3, v4, v9, v14, m[s14], m[s15])
-inline void host_blake2s_compress(uint32_t h[8], const uint8_t b[64], uint64_t t, bool last) {
-    uint32_t m[16];
-    memcpy(m, b, 64);                          // little-endian host
-    uint32_t v0 = h[0], v1 = h[1], v2 = h[2], v3 = h[3], v4 = h[4], v5 = h[5], v6 = h[6], v7 = h[7];
-    uint32_t v8 = 0x6A09E667u, v9 = 0xBB67AE85u, v10 = 0x3C6EF372u, v11 = 0xA54FF53Au;
-    uint32_t v12 = 0x510E527Fu ^ (uint32_t)t, v13 = 0x9B05688Cu ^ (uint32_t)(t >> 32), v14 = last ? ~0x1F83D9ABu : 0x1F83D9ABu, v15 = 0x5BE0CD19u;
-    B2S_ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-    B2S_ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
-    B2S_ROUND(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
-    B2S_ROUND(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
-    B2S_ROUND(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
-    B2S_ROUND(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
-    B2S_ROUND(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
-    B2S_ROUND(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
-    B2S_ROUND(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
-    B2S_ROUND(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
-    h[0] ^= v0 ^ v8; h[1] ^= v1 ^ v9; h[2] ^= v2 ^ v10; h[3] ^= v3 ^ v11; h[4] ^= v4 ^ v12; h[5] ^= v5 ^ v13; h[6] ^= v6 ^ v14; h[7] ^= v7 ^ v15;
-}
-#undef B2S_ROUND
-#undef B2S_G
-#undef B2S_ROTR
-inline void host_blake2s(const uint8_t *msg, size_t len, uint8_t out[32]) {
-    uint32_t h[8] = {0x6A09E667u ^ 0x01010020u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au, 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
-    const size_t nblocks = len ? (len + 63) / 64 : 1;
-    for (size_t blk = 0; blk + 1 < nblocks; blk++) host_blake2s_compress(h, msg + 64 * blk, (uint64_t)(blk + 1) * 64, false);
-    uint8_t b[64] = {0};
-    const size_t off = (nblocks - 1) * 64;
-    memcpy(b, msg + off, len - off);
-    host_blake2s_compress(h, b, len, true);
-    memcpy(out, h, 32);                        // little-endian host
-}
-inline void host_digest(int alg, const uint8_t *msg, size_t len, uint8_t out[32]) {
-    if (alg == GS_HASH_SHA256) host_sha256(msg, len, out); else host_blake2s(msg, len, out);
-}
 
 // ---- the wire format, read side (lib/Serializer.ts:83-144, lib/utils/serialization.ts:44-127): bounds-checked
 struct Reader {
@@ -164,48 +121,6 @@ bool merkle_check(int alg, const Bytes &root, const std::vector<uint64_t> &index
     return merkle_verify_batch(alg, root.data(), indexes, digests, mp.nodes, mp.depth);
 }
 
-// FiniteField.evalPolyAt, on host scalars
-F horner(const std::vector<F> &poly, F x) {
-    F r = 0;
-    for (size_t k = poly.size(); k-- > 0;) r = hf_add(hf_mul(r, x), poly[k]);
-    return r;
-}
-// a canonical product through the weak form where the field has one (the 128-bit flavour: no data-dependent reduction loops; the
-// other flavours: their hf_mul) — for the two loops below that run over trace-length columns
-#ifndef HF_CHAIN_MUL
-#define HF_CHAIN_MUL hf_mul
-#define HF_CHAIN_END(x) (x)
-#endif
-#ifndef HF_CHAIN_ADD
-#define HF_CHAIN_ADD hf_add
-#endif
-static inline F vf_mul(F a, F b) { return HF_CHAIN_END(HF_CHAIN_MUL(a, b)); }
-// one polynomial at many points: the coefficient loop outside, so that the points' chains are independent work for the core (a public
-// input register of an air-assembly component is a polynomial as long as the trace, and one serial chain per query is what verifying costs)
-std::vector<F> horner_many(const std::vector<F> &poly, const std::vector<F> &xs) {
-    std::vector<F> r(xs.size(), (F)0);
-    for (size_t k = poly.size(); k-- > 0;) {
-        const F c = poly[k];
-        for (size_t q = 0; q < xs.size(); q++) r[q] = HF_CHAIN_ADD(HF_CHAIN_MUL(r[q], xs[q]), c);      // weak values inside the chain
-    }
-    for (F &v : r) v = HF_CHAIN_END(v);
-    return r;
-}
-F f_div(F a, F b) { return hf_mul(a, hf_inv(b)); }
-// every element inverted with ONE field inversion (Montgomery's trick); 0 stays 0 (galois' convention)
-void batch_invert(std::vector<F> &v) {
-    std::vector<F> pre(v.size());
-    F acc = 1;
-    for (size_t i = 0; i < v.size(); i++) { pre[i] = acc; if (!hf_is_zero(v[i])) acc = hf_mul(acc, v[i]); }
-    F inv = hf_inv(acc);
-    for (size_t i = v.size(); i-- > 0;) {
-        if (hf_is_zero(v[i])) continue;
-        const F vi = v[i];
-        v[i] = hf_mul(inv, pre[i]);
-        inv = hf_mul(inv, vi);
-    }
-}
-
 // the constraint evaluator of an AIR given as a register-machine program (kind 1), on host scalars: genstark_amd/air_generic.py
 // Program.run (what the device runs in k_air_constraints).  Opcodes as in include/gstark.h.
 std::vector<F> run_program(const gs_prover_air &air, const std::vector<F> &cur, const std::vector<F> &nxt, const std::vector<F> &statics) {
@@ -233,14 +148,13 @@ std::vector<F> run_program(const gs_prover_air &air, const std::vector<F> &cur, 
 }
 
 // coefficients of the polynomial through `values` on the m-th roots of unity {g^i} (m a power of two): an inverse DFT of size m on host
-// scalars — the O(m^2) sum for the short periods of cyclic registers, a radix-2 transform for the columns of input registers (a public
-// input register of an air-assembly component can be as long as the trace)
+// scalars — the O(m^2) sum for the short periods of cyclic registers, the radix-2 transform with g^-1 and a scale by 1/m for the
+// columns of input registers (a public input register of an air-assembly component can be as long as the trace)
 std::vector<F> cyclic_poly(const std::vector<F> &values, F g) {
     const size_t m = values.size();
     const F ginv = hf_inv(g), minv = hf_inv((F)(uint64_t)m);
-    std::vector<F> out(m);
     if (m <= 32) {
-        std::vector<F> pw(m);
+        std::vector<F> out(m), pw(m);
         F cur = 1;
         for (size_t i = 0; i < m; i++) { pw[i] = cur; cur = hf_mul(cur, ginv); }
         for (size_t j = 0; j < m; j++) {
@@ -250,26 +164,9 @@ std::vector<F> cyclic_poly(const std::vector<F> &values, F g) {
         }
         return out;
     }
-    uint32_t logm = 0;
-    while ((1ull << logm) < m) logm++;
-    for (size_t i = 0; i < m; i++) {                              // bit-reversed copy, then decimation-in-time butterflies with g^-1
-        size_t r = 0;
-        for (uint32_t b = 0; b < logm; b++) r |= ((i >> b) & 1) << (logm - 1 - b);
-        out[r] = values[i];
-    }
-    for (size_t half = 1; half < m; half <<= 1) {
-        const F wlen = hf_pow(ginv, (hfe)(uint64_t)(m / (2 * half)));
-        std::vector<F> tw(half);
-        F cur = 1;
-        for (size_t k = 0; k < half; k++) { tw[k] = cur; cur = hf_mul(cur, wlen); }
-        for (size_t base = 0; base < m; base += 2 * half)
-            for (size_t k = 0; k < half; k++) {
-                const F u = out[base + k], v = vf_mul(out[base + k + half], tw[k]);
-                out[base + k] = hf_add(u, v);
-                out[base + k + half] = hf_sub(u, v);
-            }
-    }
-    for (size_t j = 0; j < m; j++) out[j] = vf_mul(out[j], minv);
+    std::vector<F> out(values);
+    host_transform(out, ginv);
+    for (size_t j = 0; j < m; j++) out[j] = hp_mul(out[j], minv);
     return out;
 }
 // the shortest power-of-two period of a column (a cyclic register of that length denotes the same polynomial): airassembly.py _shrink
@@ -299,29 +196,6 @@ void rotate_column(std::vector<F> &col, int32_t shift) {
 // m comes from the statement's assertions.  T is the statement's too, except for an AIR with input registers verified with job.steps = 0:
 // there the proof's shapes lay the trace out (capped at 2^26 steps above), and this form then allocates two T-long vectors like the
 // input-register columns do.
-// in place: a[j] <- sum_i a[i] w^(i j), w of order a.size() (a power of two)
-void host_transform(std::vector<F> &a, F w) {
-    const size_t n = a.size();
-    uint32_t lg = 0;
-    while (((size_t)1 << lg) < n) lg++;
-    for (size_t i = 0; i < n; i++) {
-        size_t r = 0;
-        for (uint32_t b = 0; b < lg; b++) r |= ((i >> b) & 1) << (lg - 1 - b);
-        if (i < r) std::swap(a[i], a[r]);
-    }
-    std::vector<F> tw(n / 2 ? n / 2 : 1);
-    F cur = 1;
-    for (size_t k = 0; k < n / 2; k++) { tw[k] = cur; cur = hf_mul(cur, w); }
-    for (size_t half = 1; half < n; half <<= 1) {
-        const size_t stride = n / (2 * half);
-        for (size_t base = 0; base < n; base += 2 * half)
-            for (size_t k = 0; k < half; k++) {
-                const F u = a[base + k], v = vf_mul(a[base + k + half], tw[k * stride]);
-                a[base + k] = hf_add(u, v);
-                a[base + k + half] = hf_sub(u, v);
-            }
-    }
-}
 // Products with an operand of at most this many coefficients are schoolbook products.  Chosen by count, not measured on its own: 64 x 64
 // is 4 096 products, the three 128-point transforms it would replace ~1 350 butterflies plus their set-up, and below it the
 // transforms' bit reversal and twiddle tables outweigh the difference.
@@ -335,8 +209,8 @@ std::vector<F> poly_product(const std::vector<F> &a, const std::vector<F> &b, F 
     if (std::min(a.size(), b.size()) <= BOUNDARY_SCHOOLBOOK_MAX) {
         std::vector<F> out(len, (F)0);
         for (size_t i = 0; i < a.size(); i++)
-            for (size_t j = 0; j < b.size(); j++) out[i + j] = HF_CHAIN_ADD(out[i + j], HF_CHAIN_MUL(a[i], b[j]));
-        for (F &v : out) v = HF_CHAIN_END(v);
+            for (size_t j = 0; j < b.size(); j++) out[i + j] = hf_add_weak(out[i + j], hf_mul_weak(a[i], b[j]));
+        for (F &v : out) v = hf_canon(v);
         return out;
     }
     uint64_t n = 1;
@@ -347,22 +221,17 @@ std::vector<F> poly_product(const std::vector<F> &a, const std::vector<F> &b, F 
     fa.resize(n, (F)0); fb.resize(n, (F)0);
     host_transform(fa, w);
     host_transform(fb, w);
-    for (uint64_t i = 0; i < n; i++) fa[i] = vf_mul(fa[i], fb[i]);
+    for (uint64_t i = 0; i < n; i++) fa[i] = hp_mul(fa[i], fb[i]);
     host_transform(fa, hf_pow(w, (hfe)(n - 1)));
     const F ninv = hf_inv((F)n);
     fa.resize(len);
-    for (F &v : fa) v = vf_mul(v, ninv);
+    for (F &v : fa) v = hp_mul(v, ninv);
     return fa;
 }
 std::vector<F> zero_poly_tree(const F *xs, size_t m, F omega, uint64_t N) {
     if (m <= BOUNDARY_SCHOOLBOOK_MAX) {
-        std::vector<F> zp(m + 1, (F)0);
-        zp[0] = 1;
-        for (size_t i = 0; i < m; i++) {
-            const F nx = hf_sub(0, xs[i]);
-            for (size_t d = i + 1; d >= 1; d--) zp[d] = hf_add(zp[d - 1], hf_mul(zp[d], nx));
-            zp[0] = hf_mul(zp[0], nx);
-        }
+        std::vector<F> zp(m + 1);
+        host_linear_product(xs, m, zp.data());
         return zp;
     }
     const size_t h = m / 2;
@@ -393,21 +262,21 @@ BoundaryValues boundary_values_tree(const Plan &plan, const Plan::Reg &r, const 
     check_many_assertions(plan, r);
     const std::vector<F> z = zero_poly_tree(r.xs.data(), m, plan.omega, plan.N);
     std::vector<F> d(T, (F)0);                                       // Z_r' ...
-    for (size_t k = 0; k < m; k++) d[k] = vf_mul((F)(uint64_t)(k + 1), z[k + 1]);
+    for (size_t k = 0; k < m; k++) d[k] = hp_mul((F)(uint64_t)(k + 1), z[k + 1]);
     host_transform(d, hf_pow(plan.omega, (hfe)plan.E));             // ... at every point of the execution domain
     std::vector<F> c(m);
     for (size_t i = 0; i < m; i++) c[i] = d[r.steps[i]];
-    batch_invert(c);
-    for (size_t i = 0; i < m; i++) c[i] = vf_mul(c[i], r.ys[i]);
+    host_batch_invert(c);
+    for (size_t i = 0; i < m; i++) c[i] = hp_mul(c[i], r.ys[i]);
     BoundaryValues out;
     out.z_at = horner_many(z, points);
     std::vector<F> diff(m);
     for (size_t q = 0; q < points.size(); q++) {
         for (size_t i = 0; i < m; i++) diff[i] = hf_sub(points[q], r.xs[i]);
-        batch_invert(diff);
+        host_batch_invert(diff);
         F sum = 0;
-        for (size_t i = 0; i < m; i++) sum = HF_CHAIN_ADD(sum, HF_CHAIN_MUL(c[i], diff[i]));
-        out.i_at.push_back(vf_mul(out.z_at[q], HF_CHAIN_END(sum)));
+        for (size_t i = 0; i < m; i++) sum = hf_add_weak(sum, hf_mul_weak(c[i], diff[i]));
+        out.i_at.push_back(hp_mul(out.z_at[q], hf_canon(sum)));
     }
     return out;
 }
@@ -714,7 +583,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
         dens.push_back(hf_sub(hf_pow(xsq[pi], (hfe)T), 1));                                            // ZeroPolynomial.ts:28-34: Z = (x^T - 1) / (x - x_last)
         for (auto &bv : bvals) dens.push_back(bv.z_at[pi]);                                         // BoundaryConstraints.ts:55-69
     }
-    batch_invert(dens);
+    host_batch_invert(dens);
     for (size_t k = 0, dc = 0; k < static_polys.size(); k++) {                // K_s(x^(T/period)) at every queried x
         if (dc < device_columns.size() && device_columns[dc].at == k) { statics_at.push_back(std::move(device_column_values[dc++])); continue; }
         std::vector<F> at(xsq.size());

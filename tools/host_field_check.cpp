@@ -8,18 +8,15 @@
 #include <stdint.h>
 #include <string.h>
 #if defined(GS_WIDE_BITS)
-#define GS_ELT 32
 #include "../genstark_amd/csrc/gf_wide.h"
-#else
-#define GS_ELT 16
 #endif
 #include "../genstark_amd/csrc/host_field.h"
 #include "../genstark_amd/csrc/host_pow.h"
 
 static hfe parse(const char *h) {
-    uint8_t b[GS_ELT];
+    uint8_t b[HF_ELT];
     const size_t n = strlen(h);
-    for (int i = 0; i < GS_ELT; i++) {
+    for (int i = 0; i < HF_ELT; i++) {
         unsigned v = 0;
         if (n >= 2 * (size_t)(i + 1)) sscanf(h + n - 2 * (i + 1), "%2x", &v);
         b[i] = (uint8_t)v;
@@ -27,9 +24,9 @@ static hfe parse(const char *h) {
     return hf_load(b);
 }
 static void show(hfe x) {
-    uint8_t b[GS_ELT];
+    uint8_t b[HF_ELT];
     hf_store(b, x);
-    for (int i = GS_ELT - 1; i >= 0; i--) printf("%02x", b[i]);
+    for (int i = HF_ELT - 1; i >= 0; i--) printf("%02x", b[i]);
 }
 #if defined(HF_HAVE_CUBE_ADD_ROWS)
 // (the row form is compiled for BMI2 cores: it inlines only into a caller built for them, like the chain's own build in air_mimc.hip)
