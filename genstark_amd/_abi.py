@@ -162,6 +162,14 @@ _RESCUE_SIGNATURES = {
 }
 RESCUE_SYMBOLS = tuple(_RESCUE_SIGNATURES)
 
+# include/gstark_tree_update.h: batches of leaf updates on the trees of both families, with every update's witness; optional in the
+# same way (genstark_amd/field_tree.py updates on host integers where a library lacks them)
+_TREE_UPDATE_SIGNATURES = {
+    'gs_hades_merkle_update': (_int, [_vp, _vp, _vp, _u64, _u32, C.POINTER(_u64), _vp, _u64, _vp, _vp]),
+    'gs_rescue_merkle_update': (_int, [_vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _u64, _vp, _vp]),
+}
+TREE_UPDATE_SYMBOLS = tuple(_TREE_UPDATE_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -176,7 +184,8 @@ def load_library(path):
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items()):
+    for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
+                              + list(_TREE_UPDATE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -11,8 +11,12 @@
 //               GS_HADES_BLOCK nodes are one launch of one workgroup (k_hades_merkle_top): the level lives in LDS, a barrier
 //               separates the levels.  Nothing here synchronises between workgroups.
 //   paths       k_hades_paths / gs_hades_merkle_paths read nothing but a node array: family-neutral (sponge_common.h), defined here.
+//   updates     gs_hades_merkle_update: the shared driver of tree_update.h over launch_hash, so an updated node is the node the tree
+//               build computes.  Its two kernels (k_tree_update_gather / _commit) know no permutation either and are defined here too.
 #include "sponge_common.h"
+#include "tree_update.h"
 #include "../../include/gstark_hades.h"
+#include "../../include/gstark_tree_update.h"
 
 #define GS_HADES_BLOCK 256
 
@@ -119,6 +123,62 @@ __global__ __launch_bounds__(256) void k_hades_paths(const fe *__restrict__ node
         const uint64_t node = l ? ((leaf >> (l - 1)) ^ 1) : leaf;
         out[t] = nodes[node * digest + e];
     }
+}
+
+// one level of a batch of updates (tree_update.h), of any tree in the heap layout: element e of update j's version ver_l[j] and of its
+// sibling's value — the version of the update the plan names, or what the node array holds — land side by side in rows[j] in
+// left/right order; the sibling is before[j][level + 1], and on level 0 the old leaf (the previous update of the same leaf, or the
+// node array) is before[j][0].  Reads of the node array only: the commit writes it, after the last level.
+__global__ __launch_bounds__(256) void k_tree_update_gather(const fe *__restrict__ nodes, uint64_t n, uint32_t digest, uint32_t depth, uint32_t level, uint64_t total,
+                                                            const uint64_t *__restrict__ idx, const int32_t *__restrict__ same, const int32_t *__restrict__ pred,
+                                                            const fe *__restrict__ ver_l, fe *__restrict__ rows, fe *__restrict__ before) {
+    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t j = t / digest, e = t % digest;
+        const uint64_t node = (n + idx[j]) >> level;
+        const int32_t p = pred[j];                                           // (the caller has moved `pred` to this level's row)
+        const fe sibling = p >= 0 ? ver_l[(uint64_t)p * digest + e] : nodes[(node ^ 1) * digest + e];
+        const uint64_t right = node & 1;
+        rows[j * 2 * digest + (right ? digest : 0) + e] = ver_l[t];
+        rows[j * 2 * digest + (right ? 0 : digest) + e] = sibling;
+        before[(j * (depth + 1) + level + 1) * digest + e] = sibling;
+        if (level == 0) {
+            const int32_t s = same[j];
+            before[j * (depth + 1) * digest + e] = s >= 0 ? ver_l[(uint64_t)s * digest + e] : nodes[node * digest + e];
+        }
+    }
+}
+
+// after the last level: the version of every node's latest toucher into the node array; item t = (level, update, element)
+__global__ __launch_bounds__(256) void k_tree_update_commit(fe *__restrict__ nodes, uint64_t n, uint32_t digest, uint32_t depth, uint64_t count, uint64_t total,
+                                                            const uint64_t *__restrict__ idx, const uint8_t *__restrict__ last, const fe *__restrict__ leaves,
+                                                            const fe *__restrict__ mid, const fe *__restrict__ roots) {
+    const uint64_t per_level = count * digest;
+    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t l = (uint32_t)(t / per_level);
+        const uint64_t at = t % per_level, j = at / digest, e = at % digest;
+        if (!last[l * count + j]) continue;
+        const fe *__restrict__ ver = l == 0 ? leaves : (l == depth ? roots : mid + (uint64_t)(l - 1) * per_level);
+        nodes[((n + idx[j]) >> l) * digest + e] = ver[at];
+    }
+}
+
+int tree_update_gather(gs_ctx *c, const fe *nodes, uint64_t n, uint32_t digest, uint32_t depth, uint32_t level, uint64_t count, const tree_update_device_plan &plan,
+                       const fe *ver_l, fe *rows, fe *before) {
+    const uint64_t total = count * digest;
+    gs_traffic(c, (5 * total + (level ? 0 : 2 * total)) * GS_ELT + count * 12, 0, "k_tree_update_gather");
+    hipLaunchKernelGGL(k_tree_update_gather, dim3(gs_grid(total)), dim3(256), 0, c->stream, nodes, n, digest, depth, level, total, plan.idx, plan.same,
+                       plan.pred + (uint64_t)level * count, ver_l, rows, before);
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
+
+int tree_update_commit(gs_ctx *c, fe *nodes, uint64_t n, uint32_t digest, uint32_t depth, uint64_t count, const tree_update_device_plan &plan, const fe *leaves,
+                       const fe *mid, const fe *roots) {
+    const uint64_t total = (uint64_t)(depth + 1) * count * digest;
+    gs_traffic(c, 2 * total * GS_ELT + (uint64_t)(depth + 1) * count, 0, "k_tree_update_commit");
+    hipLaunchKernelGGL(k_tree_update_commit, dim3(gs_grid(total)), dim3(256), 0, c->stream, nodes, n, digest, depth, count, total, plan.idx, plan.last, leaves, mid, roots);
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
 }
 
 namespace {
@@ -233,6 +293,19 @@ int gs_hades_merkle_paths(gs_ctx *c, const void *nodes, uint64_t n, uint32_t dig
     }
     gs_tmp_free(c, d_idx);                                                   // (stream-ordered cache: the launch above still reads it)
     return rc;
+}
+
+int gs_hades_merkle_update(gs_ctx *c, const gs_hades *h, void *nodes, uint64_t n, uint32_t digest, const uint64_t *indexes_host, const void *leaves, uint64_t count,
+                           void *before_out, void *roots_out) {
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "hades_merkle_update"))) return rc;
+    if (digest < 1 || digest > 2 || 2 * digest >= h->width)
+        return gs_fail(c, GS_ERR_ARG, "hades_merkle_update: nodes of %u elements (1 or 2): two of them do not fit a state of %u beside its capacity", digest, h->width);
+    if ((rc = tree_update_check(c, "hades_merkle_update", n, count, indexes_host, nodes, leaves, before_out, roots_out)) || !count) return rc;
+    return tree_update_run(c, (fe *)nodes, n, digest, indexes_host, (const fe *)leaves, count, (fe *)before_out, (fe *)roots_out, [&](const fe *rows, uint64_t cnt, fe *out) {
+        gs_traffic(c, 3 * cnt * digest * GS_ELT, cnt * hades_products(h), "k_hades_hash<%u>", h->width);
+        return launch_hash(c, h, rows, cnt, 2 * digest, digest, out);
+    });
 }
 
 }  // extern "C"

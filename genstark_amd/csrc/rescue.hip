@@ -19,8 +19,12 @@
 //   tree        node i = element 0 of modifiedSponge(node 2i, node 2i + 1), heap layout: every level is one hash launch over the level
 //               below, ordered by the stream (the level loop of sponge_common.h, down to the root).  Workgroups are one wave in both forms, so a narrow level spreads over many CUs.
 //               Nothing here synchronises between workgroups.
+//   updates     gs_rescue_merkle_update: the shared driver of tree_update.h over launch_hash with the form pick_form chooses, as the
+//               tree build does: an updated node is the node the build computes.
 #include "sponge_common.h"
+#include "tree_update.h"
 #include "../../include/gstark_rescue.h"
+#include "../../include/gstark_tree_update.h"
 #if defined(GS_FIELD_128)
 #include "gf128_lazy.h"
 #endif
@@ -327,6 +331,19 @@ int gs_rescue_merkle(gs_ctx *c, const gs_rescue *h, const void *leaves, uint64_t
         const uint32_t form = pick_form(count, 0);
         traffic(c, h, count, 2, 1, 1, form);
         return launch_hash(c, h, below, count, 2, 1, 1, form, level);
+    });
+}
+
+int gs_rescue_merkle_update(gs_ctx *c, const gs_rescue *h, void *nodes, uint64_t n, const uint64_t *indexes_host, const void *leaves, uint64_t count, void *before_out,
+                            void *roots_out) {
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "rescue_merkle_update"))) return rc;
+    if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_merkle_update: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
+    if ((rc = tree_update_check(c, "rescue_merkle_update", n, count, indexes_host, nodes, leaves, before_out, roots_out)) || !count) return rc;
+    return tree_update_run(c, (fe *)nodes, n, 1, indexes_host, (const fe *)leaves, count, (fe *)before_out, (fe *)roots_out, [&](const fe *rows, uint64_t cnt, fe *out) {
+        const uint32_t form = pick_form(cnt, 0);
+        traffic(c, h, cnt, 2, 1, 1, form);
+        return launch_hash(c, h, rows, cnt, 2, 1, 1, form, out);
     });
 }
 

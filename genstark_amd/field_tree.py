@@ -1,6 +1,7 @@
 """What the algebraic hash families (hades.py, rescue_hash.py) share above the C ABI, as csrc/sponge_common.h is below it: a parameter
 set with a device handle, and the heap-layout Merkle tree of nodes of `digest` field elements with its authentication paths.  On a
 backend whose library lacks the entry points (the tests' double) everything is computed on host integers and gives the same values."""
+import collections
 import ctypes as C
 
 from ._abi import GstarkError
@@ -68,6 +69,9 @@ def verify_path(root, index, proof, node):
     return root == v
 
 
+TreeUpdate = collections.namedtuple('TreeUpdate', 'before root')     # one record of FieldMerkleTree.updateMany
+
+
 class FieldMerkleTree:
     """2n nodes of `digest` elements in the heap layout: leaves at n .. 2n - 1, root at 1, node 0 unused.  leaves: a device Matrix of
     n x digest (a Vector of n for digest=1) — then nothing goes through host integers —, or n host values.  A subclass names itself
@@ -78,22 +82,7 @@ class FieldMerkleTree:
     def __init__(self, hash, leaves, digest):
         f = hash.field
         self.hash, self.field, self.digest = hash, f, digest
-        if isinstance(leaves, Vector):
-            if digest != 1:
-                raise GstarkError(f'{self._who}: a Vector holds leaves of one element (digest=1)')
-            n = leaves.length
-        elif isinstance(leaves, Matrix):
-            if leaves.colCount != digest:
-                raise GstarkError(f'{self._who}: the leaf matrix has {leaves.colCount} columns, the nodes {digest} elements')
-            n = leaves.rowCount
-        else:
-            try:
-                leaves = [[int(v) % f.modulus] for v in leaves] if digest == 1 else [[int(v) % f.modulus for v in leaf] for leaf in leaves]
-            except TypeError:
-                leaves = self._unreadable
-            if any(len(leaf) != digest for leaf in leaves):
-                raise GstarkError(f'{self._who}: every leaf has {digest} elements')
-            n = len(leaves)
+        leaves, n = self._readLeaves(leaves)
         if n < 2 or n & (n - 1):
             raise GstarkError(f'{self._who}: {n} leaves: the number of leaves is a power of two, at least 2')
         self.leafCount, self.depth = n, n.bit_length() - 1
@@ -109,6 +98,26 @@ class FieldMerkleTree:
             for i in range(n - 1, 0, -1):
                 nodes[i] = self._node(nodes[2 * i], nodes[2 * i + 1])
             self._host = nodes
+
+    def _readLeaves(self, leaves):
+        """(leaves, how many): a device Vector or Matrix as it is, host values as rows of `digest` integers — the constructor's leaves
+        and updateMany's"""
+        f, digest = self.field, self.digest
+        if isinstance(leaves, Vector):
+            if digest != 1:
+                raise GstarkError(f'{self._who}: a Vector holds leaves of one element (digest=1)')
+            return leaves, leaves.length
+        if isinstance(leaves, Matrix):
+            if leaves.colCount != digest:
+                raise GstarkError(f'{self._who}: the leaf matrix has {leaves.colCount} columns, the nodes {digest} elements')
+            return leaves, leaves.rowCount
+        try:
+            leaves = [[int(v) % f.modulus] for v in leaves] if digest == 1 else [[int(v) % f.modulus for v in leaf] for leaf in leaves]
+        except TypeError:
+            leaves = self._unreadable
+        if any(len(leaf) != digest for leaf in leaves):
+            raise GstarkError(f'{self._who}: every leaf has {digest} elements')
+        return leaves, len(leaves)
 
     def _shape(self, node):                  # a node as the reference's classes hold it: a pair, or one integer
         return node[0] if self.digest == 1 else tuple(node)
@@ -143,6 +152,48 @@ class FieldMerkleTree:
         self.field.backend.call('gs_hades_merkle_paths', C.c_void_p(self.deviceNodes.ptr), n, d, (C.c_uint64 * len(indexes))(*indexes), len(indexes), C.c_void_p(out.ptr))
         rows = _rows(out)
         return [[self._shape(r) for r in rows[k * per:(k + 1) * per]] for k in range(len(indexes))]
+
+    def update(self, index, leaf):
+        """updateMany([index], [leaf])[0]"""
+        return self.updateMany([index], [leaf])[0]
+
+    def updateMany(self, indexes, leaves):
+        """Sets leaf indexes[j] to leaves[j] for j = 0, 1, .. in that order (repeated indexes allowed) and returns one TreeUpdate per
+        update: `before`, what prove(indexes[j]) would have returned just before update j (the old leaf, then its siblings bottom-up),
+        and `root`, the root just after it — the witness of the reference's ComputeMerkleUpdate, whose old root is the update before's
+        `root` (this tree's root at the call for the first).  Afterwards root, nodes, prove and proveMany see the last tree.  On the
+        device: one upload of the leaves, a hash launch per level over the whole batch, one read-back of all witnesses and roots."""
+        indexes = [int(i) for i in indexes]
+        leaves, count = self._readLeaves(leaves)
+        if leaves is self._unreadable:
+            raise GstarkError(f'{self._who}: every leaf has {self.digest} elements')
+        n, per = self.leafCount, self.depth + 1
+        if count != len(indexes):
+            raise GstarkError(f'{self._who}: {len(indexes)} indexes and {count} leaves: an update is one of each')
+        if any(not 0 <= i < n for i in indexes):
+            raise GstarkError(f'{self._who}: an index is outside of the {n} leaves')
+        if not count:
+            return []
+        if self.deviceNodes is None:
+            if not isinstance(leaves, list):
+                leaves = _rows(leaves)
+            nodes, out = self._host, []
+            for i, leaf in zip(indexes, leaves):
+                at = n + i
+                before = [self._shape(nodes[at])] + [self._shape(nodes[(at >> l) ^ 1]) for l in range(self.depth)]
+                nodes[at] = list(leaf)
+                while at > 1:
+                    at >>= 1
+                    nodes[at] = self._node(nodes[2 * at], nodes[2 * at + 1])
+                out.append(TreeUpdate(before, self._shape(nodes[1])))
+            return out
+        if not hasattr(self.field.backend.lib, self._updateEntry):       # a tree built on the device is updated there: no quiet host path
+            raise GstarkError(f'{self._who}: the library has no {self._updateEntry} (include/gstark_tree_update.h)')
+        src = leaves if isinstance(leaves, (Matrix, Vector)) else self.field.newMatrixFrom(leaves)
+        before, roots = self._newNodes(count * per), self._newNodes(count)
+        self._updateOnDevice((C.c_uint64 * count)(*indexes), count, src, before, roots)
+        rows, roots = _rows(before), _rows(roots)
+        return [TreeUpdate([self._shape(r) for r in rows[j * per:(j + 1) * per]], self._shape(roots[j])) for j in range(count)]
 
 
 def _rows(array):                            # the nodes of a device array as rows of `digest` integers

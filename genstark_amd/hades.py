@@ -86,6 +86,12 @@ class HadesMerkleTree(FieldMerkleTree):
     def _buildOnDevice(self, src, out):
         self.field.backend.call('gs_hades_merkle', self.hash.handle(), C.c_void_p(src.ptr), self.leafCount, self.digest, C.c_void_p(out.ptr))
 
+    _updateEntry = 'gs_hades_merkle_update'
+
+    def _updateOnDevice(self, indexes, count, src, before, roots):
+        self.field.backend.call(self._updateEntry, self.hash.handle(), C.c_void_p(self.deviceNodes.ptr), self.leafCount, self.digest, indexes, C.c_void_p(src.ptr), count,
+                                C.c_void_p(before.ptr), C.c_void_p(roots.ptr))
+
     def _node(self, left, right):
         return self.hash.hash(left + right)[:self.digest]
 

@@ -155,6 +155,12 @@ class RescueMerkleTree(FieldMerkleTree):
     def _buildOnDevice(self, src, out):
         self.field.backend.call('gs_rescue_merkle', self.hash.handle(), C.c_void_p(src.ptr), self.leafCount, C.c_void_p(out.ptr))
 
+    _updateEntry = 'gs_rescue_merkle_update'
+
+    def _updateOnDevice(self, indexes, count, src, before, roots):
+        self.field.backend.call(self._updateEntry, self.hash.handle(), C.c_void_p(self.deviceNodes.ptr), self.leafCount, indexes, C.c_void_p(src.ptr), count,
+                                C.c_void_p(before.ptr), C.c_void_p(roots.ptr))
+
     def _node(self, left, right):
         return [self.hash.hash2(left[0], right[0])]
 

@@ -1,7 +1,8 @@
 'use strict';
 // js/field_tree.js — what js/hades.js and js/rescue.js share above the addon's table: a device handle made on first use and destroyed
 // when its owner is collected, one permutation per row of a device Matrix, and the heap-layout Merkle tree of nodes of `digest` field
-// elements with its paths (the gather is the family-neutral gs_hades_merkle_paths: it reads nothing but the node array).
+// elements with its paths (the gather is the family-neutral gs_hades_merkle_paths: it reads nothing but the node array) and its batched
+// updates (include/gstark_tree_update.h: update / updateMany return every update's witness).
 const { Matrix, Vector } = require('./galois.js');
 
 /** a registry that destroys the handle of a collected owner through `symbol` (null where the engine has none) */
@@ -14,6 +15,13 @@ function destroyRegistry(symbol) {
 function needDevice(field, family, what) {
     if (!field.lib.has || !field.lib.has(`gs_${family}_hash`)) {
         throw new Error(`the library of the field of ${field.modulus} elements has no gs_${family}_* entry points (include/gstark_${family}.h): ${what} hashes and trees are not computed on this device library`);
+    }
+}
+
+/** throws when the field's library lacks `symbol` of include/gstark_tree_update.h (optional in the same way) */
+function needUpdate(field, symbol) {
+    if (!field.lib.has || !field.lib.has(symbol)) {
+        throw new Error(`the library of the field of ${field.modulus} elements has no ${symbol} entry point (include/gstark_tree_update.h): trees are not updated on this device library`);
     }
 }
 
@@ -41,13 +49,14 @@ function hashMany(field, symbol, handle, rows, digest, ...options) {
     return out;
 }
 
-/** the tree over the device leaves `src` (the caller has checked that they are the field's: field._own), built by buildCall(handle, src, n, deviceNodes); newNodes(count): an array of the kind deviceNodes is */
+/** the tree over the device leaves `src` (the caller has checked that they are the field's: field._own), built by buildCall(handle, src, n, deviceNodes); newNodes(count): an array of the kind deviceNodes is;
+ *  update: { symbol, call(handle, deviceNodes, n, indexes, leaves, count, before, roots) } — the family's entry of include/gstark_tree_update.h */
 class DeviceTree {
-    constructor(field, handle, digest, src, newNodes, buildCall) {
+    constructor(field, handle, digest, src, newNodes, buildCall, update) {
         const n = src instanceof Vector ? src.length : src.rowCount;
         this.field = field; this.digest = digest; this.leafCount = n;
         this.depth = Math.round(Math.log2(n));
-        this._newNodes = newNodes;
+        this._newNodes = newNodes; this._handle = handle; this._update = update;
         this.deviceNodes = newNodes(2 * n);
         buildCall(handle, src, n, this.deviceNodes);
     }
@@ -64,6 +73,27 @@ class DeviceTree {
         const values = this._values(out);
         return indexes.map((_, k) => values.slice(k * per, (k + 1) * per));
     }
+    update(index, leaf) { return this.updateMany([index], [leaf])[0]; }
+    /** sets leaf indexes[j] to leaves[j], j = 0, 1, .. in that order (repeats allowed); per update { before, root }: prove(indexes[j]) as it
+     *  stood just before update j, and the root just after it (the witness of ComputeMerkleUpdate).  One upload, one launch sequence, one read-back. */
+    updateMany(indexes, leaves) {
+        needUpdate(this.field, this._update.symbol);
+        const count = indexes.length, single = this.deviceNodes instanceof Vector;
+        let src = leaves;
+        if (Array.isArray(leaves)) {
+            if (leaves.length !== count) throw new Error(`${count} indexes and ${leaves.length} leaves: an update is one of each`);
+            if (!count) return [];
+            src = single ? this.field.newVectorFrom(leaves) : this.field.newMatrixFrom(this.digest === 1 ? leaves.map(v => [v]) : leaves);
+        }
+        this.field._own(src);
+        if ((src instanceof Vector ? src.length : src.rowCount) !== count) throw new Error(`${count} indexes and ${src instanceof Vector ? src.length : src.rowCount} leaves: an update is one of each`);
+        if ((src instanceof Vector ? 1 : src.colCount) !== this.digest) throw new Error(`the leaves have ${this.digest} element${this.digest > 1 ? 's' : ''} each`);
+        if (!count) return [];
+        const per = this.depth + 1, before = this._newNodes(count * per), roots = this._newNodes(count);
+        this._update.call(this._handle, this.deviceNodes, this.leafCount, indexes, src, count, before, roots);
+        const values = this._values(before), after = this._values(roots);
+        return indexes.map((_, j) => ({ before: values.slice(j * per, (j + 1) * per), root: after[j] }));
+    }
 }
 
 /** a path (the leaf, then its siblings bottom-up) against a root: node(left, right) level by level, sides by the index bits */
@@ -75,4 +105,4 @@ function verifyPath(root, index, proof, node, same = (a, b) => a === b) {
     return same(root, v);
 }
 
-module.exports = { destroyRegistry, needDevice, lazyHandle, hashMany, DeviceTree, verifyPath };
+module.exports = { destroyRegistry, needDevice, needUpdate, lazyHandle, hashMany, DeviceTree, verifyPath };

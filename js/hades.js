@@ -2,8 +2,9 @@
 // js/hades.js — the Poseidon helpers of the reference's examples/poseidon/utils.ts with the bulk work on the device
 // (include/gstark_hades.h through the addon's table): createHash(field, exp, rf, rp, stateWidth, rc?) returns the example's hash function
 // (BigInt arithmetic on the host, as upstream) which also carries .hashMany(matrix, digest) — one permutation per row in one launch —,
-// and MerkleTree / MerkleTree2 have the example's members (nodes, root, prove, static verify) plus proveMany(indexes): the tree is built
-// by the device, the paths of any number of leaves come back in one read-back.  `field` is a PrimeField of js/galois.js.  A field whose
+// and MerkleTree / MerkleTree2 have the example's members (nodes, root, prove, static verify) plus proveMany(indexes) and update /
+// updateMany(indexes, leaves): the tree is built and updated by the device, the paths of any number of leaves and the witnesses of any
+// number of updates come back in one read-back.  `field` is a PrimeField of js/galois.js.  A field whose
 // library lacks the entry points (they are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const crypto = require('crypto');
 const { Matrix, Vector } = require('./galois.js');
@@ -75,7 +76,9 @@ class HadesTree extends DeviceTree {
         field._own(src);
         if ((src instanceof Vector ? 1 : src.colCount) !== digest) throw new Error(`the leaves have ${digest} element${digest > 1 ? 's' : ''} each`);
         super(field, hash.handle(), digest, src, count => new Matrix(field, count, digest),
-            (handle, leaves, n, nodes) => field.lib.call('gs_hades_merkle', field.ctx, handle, leaves.ptr, n, digest, nodes.ptr));
+            (handle, leaves, n, nodes) => field.lib.call('gs_hades_merkle', field.ctx, handle, leaves.ptr, n, digest, nodes.ptr),
+            { symbol: 'gs_hades_merkle_update', call: (handle, nodes, n, indexes, leaves, count, before, roots) =>
+                field.lib.call('gs_hades_merkle_update', field.ctx, handle, nodes.ptr, n, digest, indexes, leaves.ptr, count, before.ptr, roots.ptr) });
         this.hash = hash;
     }
 }

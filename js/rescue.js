@@ -109,7 +109,9 @@ class MerkleTree extends DeviceTree {      // utils.ts:232-273, built by the dev
         if (!(src instanceof Vector)) throw new Error('the leaves are an array of BigInts or a Vector');
         field._own(src);
         super(field, rescue.handle(), 1, src, count => new Vector(field, count),
-            (handle, leaves, n, nodes) => field.lib.call('gs_rescue_merkle', field.ctx, handle, leaves.ptr, n, nodes.ptr));
+            (handle, leaves, n, nodes) => field.lib.call('gs_rescue_merkle', field.ctx, handle, leaves.ptr, n, nodes.ptr),
+            { symbol: 'gs_rescue_merkle_update', call: (handle, nodes, n, indexes, leaves, count, before, roots) =>
+                field.lib.call('gs_rescue_merkle_update', field.ctx, handle, nodes.ptr, n, indexes, leaves.ptr, count, before.ptr, roots.ptr) });
         this.rescue = rescue;
     }
     /** hash: a function of two values (rescue.hash2) */

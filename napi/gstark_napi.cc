@@ -128,6 +128,9 @@ const FnDesc kFns[] = {
     {"gs_rescue_destroy", "cp"},
     {"gs_rescue_hash", "cppuiiiip"},
     {"gs_rescue_merkle", "cppup"},
+    // include/gstark_tree_update.h: OPTIONAL in the same way; the handles are those of gs_hades_create / gs_rescue_create
+    {"gs_hades_merkle_update", "cppuixpupp"},
+    {"gs_rescue_merkle_update", "cppuxpupp"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
