@@ -222,6 +222,29 @@ def test_kat_rescue_4x128_through_hip_kernels(hip_backend):
     cases.check_rescue_kat(hip_backend)
 
 
+def test_corner_arithmetic(hip_backend):
+    """Every vector member on operands that take the rare branches of fe_reduce_wide (k = 1, the closing overflow of w + C) and of
+    fe_add / fe_sub, at lengths around the wave and workgroup seams (tests/field_corners.py)."""
+    import field_corners
+    field_corners.check_corner_arithmetic(hip_backend, P)
+
+
+@pytest.mark.parametrize('jit', [0, 1])
+def test_corner_products_through_the_trace_programs(hip_backend, oracle_backend, jit):
+    """The first step of every segment is a product that takes a rare branch: the interpreted transition program (csrc/air_vm.hip:
+    fe_mul) and the compiled one (csrc/air_jit.hip: its own copy of the headers, products through the lazy-limb routines) against the
+    recurrence on integers, the host trace and the oracle."""
+    import field_corners
+    from genstark_amd._abi import Backend
+    be = Backend(device=0).jit() if jit else hip_backend        # (a context of its own: the session's counts no compiled launches)
+    try:
+        got = field_corners.check_corner_trace(be, P, expect_compiled=bool(jit))
+        assert got == field_corners.check_corner_trace(oracle_backend, P)
+    finally:
+        if jit:
+            be.close()
+
+
 # ---- (b) HIP bytes == oracle bytes on the same seeded inputs ----------------------------------------------
 def _both(hip_backend, oracle_backend):
     return PrimeField(backend=hip_backend), PrimeField(backend=oracle_backend)

@@ -9,6 +9,7 @@ import random
 import pytest
 
 from conftest import ROOT, _build_oracle, native_same_bytes
+from field_corners import check_corner_arithmetic, check_corner_trace
 from genstark_amd._abi import HIP_LIB_PATHS, MODULUS_17, MODULUS_32, MODULUS_64, Backend
 from genstark_amd.air_generic import GenericAir
 from genstark_amd.errors import StarkError
@@ -82,6 +83,7 @@ def check_arithmetic(backend, q, seed):
             x = pow(w, i % m, q)
             assert got[i % m] == sum(c * pow(x, k, q) for k, c in enumerate(coeffs)) % q
         assert f.interpolateRoots(f.getPowerSeries(w, m), ev).toValues() == coeffs + [0] * (m - plen)
+    check_corner_arithmetic(backend, q)          # ... and on the operands that take the rare carries of this field's reductions
 
 
 def fibonacci_air(field, steps):
@@ -198,3 +200,17 @@ def test_small_field_hip(name):
     assert hip.name == 'hip-gfx950' and hip.modulus == FLAVOURS[name]
     check_arithmetic(hip, FLAVOURS[name], 11)
     assert check_starks(hip, name) == check_starks(oracle_for(name), name)
+
+
+@pytest.mark.gpu
+def test_corner_products_through_the_trace_programs_q64():
+    """The first step of every segment is a product that takes a rare branch of gfs_mul: the interpreted transition program
+    (csrc/air_vm.hip) and the compiled one (csrc/air_jit.hip, its own copy of gf_small.h) against the recurrence on integers."""
+    plain, compiled = hip_for('q64'), hip_for('q64').jit()
+    try:
+        want = check_corner_trace(plain, MODULUS_64)
+        assert check_corner_trace(compiled, MODULUS_64, expect_compiled=True) == want
+        assert plain.jit_launches == 0
+    finally:
+        compiled.close()
+        plain.close()

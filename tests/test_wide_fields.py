@@ -17,6 +17,7 @@ from genstark_amd.field import PrimeField
 from genstark_amd.hostfield import HostField
 from genstark_amd.pointmul import ec_multiply, point_mul_air, to_bits
 from genstark_amd._mirror.stark import Stark
+from field_corners import check_corner_trace
 from test_small_fields import check_arithmetic
 
 FLAVOURS = {'p256': MODULUS_256, 'p224': MODULUS_224}
@@ -220,6 +221,21 @@ def test_compiled_point_multiplication_equals_interpreted():
         assert compiled.jit_launches == 0
         assert point_mul16(compiled) == want
         assert compiled.jit_launches >= 2 and plain.jit_launches == 0
+    finally:
+        compiled.close()
+        plain.close()
+
+
+@pytest.mark.gpu
+def test_corner_products_through_the_trace_programs_p224():
+    """The first step of every segment is a product that takes the carry out of the second fold or the closing subtraction of gf_wide.h:
+    the interpreted transition program (csrc/air_vm.hip) and the compiled one (csrc/air_jit.hip, its own copy of the header) against
+    the recurrence on integers."""
+    plain, compiled = hip_for('p224'), hip_for('p224').jit()
+    try:
+        want = check_corner_trace(plain, MODULUS_224)
+        assert check_corner_trace(compiled, MODULUS_224, expect_compiled=True) == want
+        assert plain.jit_launches == 0
     finally:
         compiled.close()
         plain.close()
