@@ -170,6 +170,14 @@ _TREE_UPDATE_SIGNATURES = {
 }
 TREE_UPDATE_SYMBOLS = tuple(_TREE_UPDATE_SIGNATURES)
 
+# include/gstark_tree_verify.h: the roots that batches of authentication paths imply, for the trees of both families; optional in the
+# same way (genstark_amd/field_tree.py walks the paths on host integers where a library lacks the family)
+_TREE_VERIFY_SIGNATURES = {
+    'gs_hades_merkle_path_roots': (_int, [_vp, _vp, _vp, _u32, _u32, C.POINTER(_u64), _vp, _u64, _vp]),
+    'gs_rescue_merkle_path_roots': (_int, [_vp, _vp, _vp, _u32, C.POINTER(_u64), _vp, _u64, _vp]),
+}
+TREE_VERIFY_SYMBOLS = tuple(_TREE_VERIFY_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -185,7 +193,7 @@ def load_library(path):
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
-                              + list(_TREE_UPDATE_SIGNATURES.items())):
+                              + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -13,10 +13,14 @@
 //   paths       k_hades_paths / gs_hades_merkle_paths read nothing but a node array: family-neutral (sponge_common.h), defined here.
 //   updates     gs_hades_merkle_update: the shared driver of tree_update.h over launch_hash, so an updated node is the node the tree
 //               build computes.  Its two kernels (k_tree_update_gather / _commit) know no permutation either and are defined here too.
+//   path roots  gs_hades_merkle_path_roots (tree_verify.h): one thread walks one path through all its levels in ONE launch
+//               (k_hades_path_roots), the running node in registers; the sibling of a level is read straight from the path array.
 #include "sponge_common.h"
 #include "tree_update.h"
+#include "tree_verify.h"
 #include "../../include/gstark_hades.h"
 #include "../../include/gstark_tree_update.h"
+#include "../../include/gstark_tree_verify.h"
 
 #define GS_HADES_BLOCK 256
 
@@ -110,6 +114,45 @@ __global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_merkle_top(fe *nodes,u
         }
         __syncthreads();
     }
+}
+
+// The root every path implies (tree_verify.h): thread k walks path k — paths[k] = the leaf, then `depth` siblings bottom-up, `digest`
+// elements each — from leaves[k] when `leaves` is given, else from the path's own leaf.  On level l the state is (left, right, zeros),
+// the running node on the right when bit l of idx[k] is 1, and the node above is the first `digest` elements of its permutation: what
+// k_hades_hash computes for a row of a tree level.  No staging through LDS: a level costs one load of 16 .. 64 bytes per thread against
+// the hundreds of field products of a permutation, a thread's siblings are consecutive in memory (the line one level fetches serves
+// the next levels from the cache), and a workgroup's paths — 256 x 37 x 2 elements at the limits — do not fit the LDS at all.
+// 2 * digest < W (the entry has checked it).
+template <int W>
+__global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_path_roots(const fe *__restrict__ paths, uint32_t depth, uint32_t digest, const uint64_t *__restrict__ idx,
+                                                                     const fe *__restrict__ leaves, uint64_t count, const fe *__restrict__ consts, uint32_t rf,
+                                                                     uint32_t rp, uint64_t alpha, fe *__restrict__ roots) {
+    const uint64_t k = (uint64_t)blockIdx.x * GS_HADES_BLOCK + threadIdx.x;
+    if (k >= count) return;                                                  // (nothing below crosses lanes)
+    const fe *__restrict__ path = paths + k * (depth + 1) * digest;
+    const fe *__restrict__ start = leaves ? leaves + k * digest : path;
+    const uint64_t index = idx[k];
+    fe v0 = start[0], v1 = digest > 1 ? start[1] : fe_zero();
+#pragma unroll 1
+    for (uint32_t l = 0; l < depth; l++) {
+        const fe *__restrict__ sibling = path + (uint64_t)(l + 1) * digest;
+        const fe u0 = sibling[0], u1 = digest > 1 ? sibling[1] : fe_zero();
+        const bool right = (index >> l) & 1u;
+        const fe a0 = right ? u0 : v0, a1 = right ? u1 : v1, b0 = right ? v0 : u0, b1 = right ? v1 : u1;      // left a, right b
+        fe s[W];
+#pragma unroll
+        for (int j = 2; j < W; j++) s[j] = fe_zero();
+        s[0] = a0;
+        s[1] = digest > 1 ? a1 : b0;
+        if constexpr (W > 4) {                                               // (nodes of two elements need a state of five)
+            if (digest > 1) { s[2] = b0; s[3] = b1; }
+        }
+        hades_permute<W>(s, consts, rf, rp, alpha);
+        v0 = s[0];
+        v1 = s[1];
+    }
+    roots[k * digest] = v0;
+    if (digest > 1) roots[k * digest + 1] = v1;
 }
 
 // out[path][level][e]: the leaf (level 0), then the sibling on every level from the leaves up — of any tree in the heap layout
@@ -212,6 +255,21 @@ int launch_top(gs_ctx *c, const gs_hades *h, fe *nodes, uint32_t m, uint32_t dig
     return GS_OK;
 }
 
+int launch_path_roots(gs_ctx *c, const gs_hades *h, const fe *paths, uint32_t depth, uint32_t digest, const uint64_t *idx, const fe *leaves, uint64_t count, fe *roots) {
+    const uint64_t blocks = (count + GS_HADES_BLOCK - 1) / GS_HADES_BLOCK;
+    switch (h->width) {
+#define X(W)                                                                                                                                             \
+    case W:                                                                                                                                              \
+        hipLaunchKernelGGL(k_hades_path_roots<(W < 3 ? 3 : W)>, dim3((unsigned)blocks), dim3(GS_HADES_BLOCK), 0, c->stream, paths, depth, digest, idx, leaves, count, \
+                           (const fe *)h->consts, h->rf, h->rp, h->alpha, roots);                                                                        \
+        break;
+        GS_SPONGE_WIDTHS(X)                                                   // (2 * digest < width: width 2 never gets here)
+#undef X
+    }
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
+
 // products of one permutation: the S-boxes of rf full and rp partial rounds and the matrix of every round
 uint64_t hades_products(const gs_hades *h) {
     const uint64_t w = h->width, per_pow = sponge_pow_products(h->alpha);
@@ -305,6 +363,19 @@ int gs_hades_merkle_update(gs_ctx *c, const gs_hades *h, void *nodes, uint64_t n
     return tree_update_run(c, (fe *)nodes, n, digest, indexes_host, (const fe *)leaves, count, (fe *)before_out, (fe *)roots_out, [&](const fe *rows, uint64_t cnt, fe *out) {
         gs_traffic(c, 3 * cnt * digest * GS_ELT, cnt * hades_products(h), "k_hades_hash<%u>", h->width);
         return launch_hash(c, h, rows, cnt, 2 * digest, digest, out);
+    });
+}
+
+int gs_hades_merkle_path_roots(gs_ctx *c, const gs_hades *h, const void *paths, uint32_t depth, uint32_t digest, const uint64_t *indexes_host, const void *leaves,
+                               uint64_t count, void *roots_out) {
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "hades_merkle_path_roots"))) return rc;
+    if (digest < 1 || digest > 2 || 2 * digest >= h->width)
+        return gs_fail(c, GS_ERR_ARG, "hades_merkle_path_roots: nodes of %u elements (1 or 2): two of them do not fit a state of %u beside its capacity", digest, h->width);
+    if ((rc = tree_verify_check(c, "hades_merkle_path_roots", depth, count, indexes_host, paths, roots_out)) || !count) return rc;
+    return tree_verify_run(c, indexes_host, count, [&](const uint64_t *idx) {
+        gs_traffic(c, tree_verify_bytes(depth, digest, leaves != nullptr, count), count * depth * hades_products(h), "k_hades_path_roots<%u>", h->width);
+        return launch_path_roots(c, h, (const fe *)paths, depth, digest, idx, (const fe *)leaves, count, (fe *)roots_out);
     });
 }
 

@@ -21,10 +21,14 @@
 //               Nothing here synchronises between workgroups.
 //   updates     gs_rescue_merkle_update: the shared driver of tree_update.h over launch_hash with the form pick_form chooses, as the
 //               tree build does: an updated node is the node the build computes.
+//   path roots  gs_rescue_merkle_path_roots (tree_verify.h): a path is a dependent chain of permutations, so it is walked in form 2
+//               only (k_rescue_path_roots<G>: a group of G lanes per path, every level in ONE launch); the entry's cap is form 2's limit.
 #include "sponge_common.h"
 #include "tree_update.h"
+#include "tree_verify.h"
 #include "../../include/gstark_rescue.h"
 #include "../../include/gstark_tree_update.h"
+#include "../../include/gstark_tree_verify.h"
 #if defined(GS_FIELD_128)
 #include "gf128_lazy.h"
 #endif
@@ -35,6 +39,7 @@
 #define GS_RESCUE_SPREAD_LIMIT (1ull << 20)  // form 0: form 2 up to this many permutations — measured: form 2 is the faster one at every
                                              // count from 1 to 2^20 (by 4x up to 2^14, by 2 % at 2^20), no crossover found (profiles/rescue.md)
 #define GS_RESCUE_SPREAD_MAX (1ull << 24)    // form 2: the grid is count * G / 64 workgroups
+static_assert(GS_TREE_VERIFY_MAX <= GS_RESCUE_SPREAD_LIMIT, "the path walk exists in form 2 only: its cap is the count up to which form 2 is the faster one");
 
 struct gs_rescue {
     gs_ctx *ctx;
@@ -197,7 +202,64 @@ __global__ __launch_bounds__(GS_RESCUE_BLOCK) void k_rescue_spread(const fe *__r
     if (live && j < digest) out[perm * digest + j] = x;
 }
 
+// The root every path implies (tree_verify.h), in form 2: an aligned group of G lanes walks one path, lane j holding element j of the
+// state.  paths[k] = the leaf, then `depth` siblings bottom-up, one element each; the walk starts from leaves[k] when `leaves` is given.
+// Between two levels lane 0 holds the running node (element 0 of the modified sponge) and lane 1 loads the sibling; the two swap
+// values when bit l of idx[k] is 1 (the running node enters on the right), every other lane carries zero: the state (left, right,
+// zeros) of a tree level's row.  Every lane stays active to the end — the cross-lane reads need the whole wave —, only the loads and
+// the final store are guarded.
+template <int G>
+__global__ __launch_bounds__(GS_RESCUE_BLOCK) void k_rescue_path_roots(const fe *__restrict__ paths, uint32_t depth, const uint64_t *__restrict__ idx,
+                                                                       const fe *__restrict__ leaves, uint64_t count, uint32_t width, const fe *__restrict__ consts,
+                                                                       uint32_t rounds, uint64_t alpha, const uint32_t *__restrict__ sched, uint32_t nops, uint32_t table,
+                                                                       fe *__restrict__ roots) {
+    const uint32_t lane = threadIdx.x, j = lane % G, base = lane - j;
+    const uint64_t k = (uint64_t)blockIdx.x * (GS_RESCUE_BLOCK / G) + lane / G;
+    const bool live = k < count;
+    const uint32_t col = j < width ? j : 0;                                 // a surplus lane reads keys that exist and multiplies them by nothing
+    const fe *__restrict__ mds = consts + (uint64_t)(2 * rounds + 3) * width;
+    fe row[G];
+#pragma unroll
+    for (int i = 0; i < G; i++) row[i] = (j < width && i < (int)width) ? mds[j * width + i] : fe_zero();
+    const fe *__restrict__ path = paths + (live ? k : 0) * (depth + 1);
+    const uint64_t index = live ? idx[k] : 0;
+    fe x = (live && j == 0) ? (leaves ? leaves[k] : path[0]) : fe_zero();
+    uint32_t halves, first_key, first_inverse;
+    rescue_shape(rounds, 1, halves, first_key, first_inverse);
+#pragma unroll 1
+    for (uint32_t l = 0; l < depth; l++) {
+        const fe mine = j == 0 ? x : ((live && j == 1) ? path[l + 1] : fe_zero());      // lane 0: the running node, lane 1: the sibling
+        const fe other = rescue_lane_read(mine, (int)(base + (j ^ 1u)));
+        x = j < 2 ? (((index >> l) & 1u) ? other : mine) : fe_zero();
+        uint32_t key = first_key, inverse = first_inverse;
+#pragma unroll 1
+        for (uint32_t h = 0; h < halves; h++, key++, inverse ^= 1u) {
+            x = inverse ? rescue_inv_sbox<rescue_chain>(x, sched, nops, table) : fe_pow_u64(x, alpha);
+            fe acc = consts[(uint64_t)key * width + col];
+#pragma unroll
+            for (int i = 0; i < G; i++) acc = fe_add(acc, fe_mul(row[i], rescue_lane_read(x, (int)(base + i))));
+            x = j < width ? acc : fe_zero();
+        }
+    }
+    if (live && j == 0) roots[k] = x;
+}
+
 namespace {
+
+uint32_t spread_group(const gs_rescue *h) { return h->width <= 2 ? 2u : (h->width <= 4 ? 4u : 8u); }
+
+int launch_path_roots(gs_ctx *c, const gs_rescue *h, const fe *paths, uint32_t depth, const uint64_t *idx, const fe *leaves, uint64_t count, fe *roots) {
+    const uint32_t g = spread_group(h);                                      // (width 3 .. 8: 4 or 8)
+    const uint64_t per = GS_RESCUE_BLOCK / g, blocks = (count + per - 1) / per;
+#define X(G)                                                                                                                                          \
+    hipLaunchKernelGGL(k_rescue_path_roots<G>, dim3((unsigned)blocks), dim3(GS_RESCUE_BLOCK), 0, c->stream, paths, depth, idx, leaves, count, h->width, \
+                       (const fe *)h->consts, h->rounds, h->alpha, h->sched, h->nops, h->table, roots)
+    if (g == 4) X(4);
+    else X(8);
+#undef X
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
 
 int launch_hash(gs_ctx *c, const gs_rescue *h, const fe *in, uint64_t count, uint32_t arity, uint32_t digest, uint32_t modified, uint32_t form, fe *out) {
     if (form == 2) {
@@ -344,6 +406,18 @@ int gs_rescue_merkle_update(gs_ctx *c, const gs_rescue *h, void *nodes, uint64_t
         const uint32_t form = pick_form(cnt, 0);
         traffic(c, h, cnt, 2, 1, 1, form);
         return launch_hash(c, h, rows, cnt, 2, 1, 1, form, out);
+    });
+}
+
+int gs_rescue_merkle_path_roots(gs_ctx *c, const gs_rescue *h, const void *paths, uint32_t depth, const uint64_t *indexes_host, const void *leaves, uint64_t count,
+                                void *roots_out) {
+    int rc;
+    if ((rc = sponge_check_handle(c, h, "rescue_merkle_path_roots"))) return rc;
+    if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_merkle_path_roots: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
+    if ((rc = tree_verify_check(c, "rescue_merkle_path_roots", depth, count, indexes_host, paths, roots_out)) || !count) return rc;
+    return tree_verify_run(c, indexes_host, count, [&](const uint64_t *idx) {
+        gs_traffic(c, tree_verify_bytes(depth, 1, leaves != nullptr, count), count * depth * rescue_products(h, 1), "k_rescue_path_roots<%u>", spread_group(h));
+        return launch_path_roots(c, h, (const fe *)paths, depth, idx, (const fe *)leaves, count, (fe *)roots_out);
     });
 }
 

@@ -3,6 +3,7 @@ set with a device handle, and the heap-layout Merkle tree of nodes of `digest` f
 backend whose library lacks the entry points (the tests' double) everything is computed on host integers and gives the same values."""
 import collections
 import ctypes as C
+import types
 
 from ._abi import GstarkError
 from .field import Matrix, Vector
@@ -59,14 +60,19 @@ class DeviceParameters:
         return out
 
 
-def verify_path(root, index, proof, node):
-    """a path (the leaf, then its siblings bottom-up) against a root: node(left, right) level by level, sides by the index bits"""
+def path_root(index, proof, node):
+    """the root a path (the leaf, then its siblings bottom-up) implies: node(left, right) level by level, sides by the index bits"""
     index += 1 << (len(proof) - 1)
     v = proof[0]
     for sibling in proof[1:]:
         v = node(sibling, v) if index & 1 else node(v, sibling)
         index >>= 1
-    return root == v
+    return v
+
+
+def verify_path(root, index, proof, node):
+    """a path against a root"""
+    return root == path_root(index, proof, node)
 
 
 TreeUpdate = collections.namedtuple('TreeUpdate', 'before root')     # one record of FieldMerkleTree.updateMany
@@ -78,6 +84,7 @@ class FieldMerkleTree:
     (`_who`) and has `_newNodes(count)` (the kind of array deviceNodes is), `_buildOnDevice(src, out)` and `_node(left, right)` on host
     integers.  The path gather is the family-neutral one (gs_hades_merkle_paths reads nothing but the node array)."""
     _unreadable = [[]]                       # what leaves that cannot be read as host values count as
+    _digest = None                           # the size of a node where the family fixes it (pathRoots over device paths)
 
     def __init__(self, hash, leaves, digest):
         f = hash.field
@@ -194,6 +201,127 @@ class FieldMerkleTree:
         self._updateOnDevice((C.c_uint64 * count)(*indexes), count, src, before, roots)
         rows, roots = _rows(before), _rows(roots)
         return [TreeUpdate([self._shape(r) for r in rows[j * per:(j + 1) * per]], self._shape(roots[j])) for j in range(count)]
+
+    # ---- the consuming side (include/gstark_tree_verify.h): a verifier holds a root and a hash, not a tree ------------------------
+    @classmethod
+    def pathRoots(cls, hash, indexes, proofs, leaves=None, digest=None):
+        """The root each path implies, in the shape `root` has (an integer for nodes of one element, a tuple for two).  proofs: paths as
+        prove / proveMany return them (the leaf, then its siblings bottom-up), or a device Matrix of one row of (depth + 1) * digest
+        elements per path — the layout the path gather and updateMany's witnesses have on the device.  indexes[k] is the leaf index of
+        path k.  leaves (a list, or a device array as in updateMany): path k starts from leaves[k] instead of its own leaf.  digest is
+        that of the first path's leaf when not given.  On the device: ONE launch walks every level of every path."""
+        indexes, depth, digest, paths = cls._readPaths(hash, indexes, proofs, digest)
+        return cls._impliedRoots(hash, indexes, depth, digest, paths, leaves)
+
+    @classmethod
+    def verifyMany(cls, root, indexes, proofs, hash):
+        """verify(root, indexes[k], proofs[k], ..) for every k: one bool per path"""
+        root, digest = cls._readRoot(hash, root)
+        return [r == root for r in cls.pathRoots(hash, indexes, proofs, digest=digest)]
+
+    @classmethod
+    def verifyUpdates(cls, old_root, indexes, leaves, records, hash):
+        """One bool per record of updateMany(indexes, leaves) on a tree whose root was old_root: update j is valid when records[j].before
+        at indexes[j] implies the root before it (old_root, then records[j - 1].root as claimed) AND the same siblings under leaves[j]
+        imply records[j].root.  Two device calls in all."""
+        old_root, digest = cls._readRoot(hash, old_root)
+        records = list(records)
+        claimed = [cls._readRoot(hash, r.root)[0] for r in records]
+        indexes, depth, digest, paths = cls._readPaths(hash, indexes, [r.before for r in records], digest)
+        if not indexes:
+            cls._impliedRoots(hash, indexes, depth, digest, paths, leaves)       # (the refusals of leaves that are no leaves of no updates)
+            return []
+        if cls._walksOnDevice(hash) and not isinstance(paths, Matrix):
+            paths = hash.field.newMatrixFrom([[v for node in path for v in node] for path in paths])      # one upload serves both calls
+        before = cls._impliedRoots(hash, indexes, depth, digest, paths, None)
+        after = cls._impliedRoots(hash, indexes, depth, digest, paths, leaves)
+        return [b == was and a == now for b, was, a, now in zip(before, [old_root] + claimed[:-1], after, claimed)]
+
+    @classmethod
+    def _walksOnDevice(cls, hash):
+        """False on a library without the family's entry points (the tests' double): host integers.  A hash that lives on the device
+        walks its paths there: no quiet host path where only the entry of include/gstark_tree_verify.h is missing."""
+        if not hash.onDevice:
+            return False
+        if not hasattr(hash.field.backend.lib, cls._pathRootsEntry):
+            raise GstarkError(f'{cls._who}: the library has no {cls._pathRootsEntry} (include/gstark_tree_verify.h)')
+        return True
+
+    @classmethod
+    def _readRoot(cls, hash, root):
+        """(the root mod p in the shape `root` has, its digest)"""
+        p = hash.field.modulus
+        try:
+            return (int(root) % p, 1) if not isinstance(root, (tuple, list)) else (tuple(int(v) % p for v in root), len(root))
+        except (TypeError, ValueError):
+            raise GstarkError(f'{cls._who}: a root is one integer or a tuple of integers') from None
+
+    @classmethod
+    def _readPaths(cls, hash, indexes, proofs, digest):
+        """(indexes, depth, digest, paths): paths the device Matrix as it is, or per path depth + 1 rows of `digest` integers mod p"""
+        p = hash.field.modulus
+        indexes = [int(i) for i in indexes]
+        if isinstance(proofs, Matrix):
+            digest = cls._digest if digest is None else digest
+            if digest is None:
+                raise GstarkError(f'{cls._who}: paths on the device do not tell the size of a node: pass digest=')
+            cls._checkDigest(hash, digest)
+            count, depth = proofs.rowCount, proofs.colCount // digest - 1
+            if proofs.colCount % digest or depth < 1:
+                raise GstarkError(f'{cls._who}: a row of {proofs.colCount} elements is no leaf of {digest} with at least one sibling')
+            paths = proofs
+        else:
+            proofs = [list(path) for path in proofs]
+            count = len(proofs)
+            if digest is None:
+                first = proofs[0][0] if proofs and proofs[0] else 0
+                digest = len(first) if isinstance(first, (tuple, list)) else 1
+            cls._checkDigest(hash, digest)
+            if any(len(path) != len(proofs[0]) for path in proofs):
+                raise GstarkError(f'{cls._who}: the paths have unequal lengths: one call checks paths of one depth')
+            depth = len(proofs[0]) - 1 if proofs else 1
+            if depth < 1:
+                raise GstarkError(f'{cls._who}: a path is a leaf and at least one sibling')
+            try:
+                paths = [[[int(node) % p] if digest == 1 else [int(v) % p for v in node] for node in path] for path in proofs]
+            except TypeError:
+                paths = [[[]]]
+            if any(len(node) != digest for path in paths for node in path):
+                raise GstarkError(f'{cls._who}: every node of a path has {digest} element{"s" if digest > 1 else ""}')
+        if count != len(indexes):
+            raise GstarkError(f'{cls._who}: {len(indexes)} indexes and {count} paths: a path is checked at one index')
+        for i in indexes:
+            if not 0 <= i < 1 << depth:
+                raise GstarkError(f'{cls._who}: index {i} is outside of the {1 << depth} leaves of a path of {depth} siblings')
+        return indexes, depth, digest, paths
+
+    @classmethod
+    def _impliedRoots(cls, hash, indexes, depth, digest, paths, leaves):
+        f, count = hash.field, len(indexes)
+        reader = types.SimpleNamespace(hash=hash, field=f, digest=digest, _who=cls._who, _unreadable=cls._unreadable)      # what _readLeaves and _node look at
+        shape = (lambda node: node[0]) if digest == 1 else tuple
+        if leaves is not None:
+            leaves, given = cls._readLeaves(reader, leaves)
+            if leaves is cls._unreadable or given != count:
+                raise GstarkError(f'{cls._who}: {count} paths and {given} leaves of {digest} element{"s" if digest > 1 else ""}: a path starts from one leaf')
+        if not count:
+            return []
+        if not cls._walksOnDevice(hash):
+            if isinstance(paths, Matrix):
+                paths = [[row[l * digest:(l + 1) * digest] for l in range(depth + 1)] for row in paths.toValues()]
+            if leaves is not None:
+                starts = leaves if isinstance(leaves, list) else _rows(leaves)
+                paths = [[list(leaf)] + path[1:] for leaf, path in zip(starts, paths)]
+            return [shape(path_root(i, path, lambda left, right: cls._node(reader, left, right))) for i, path in zip(indexes, paths)]
+        be = f.backend
+        if not isinstance(paths, Matrix):
+            paths = f.newMatrixFrom([[v for node in path for v in node] for path in paths])
+        if leaves is not None and not isinstance(leaves, (Matrix, Vector)):
+            leaves = f.newMatrixFrom(leaves)
+        roots = Matrix(be, count, digest)
+        cls._pathRootsOnDevice(hash, C.c_void_p(paths.ptr), depth, digest, (C.c_uint64 * count)(*indexes), C.c_void_p(leaves.ptr) if leaves is not None else None,
+                               count, C.c_void_p(roots.ptr))
+        return [shape(r) for r in roots.toValues()]
 
 
 def _rows(array):                            # the nodes of a device array as rows of `digest` integers

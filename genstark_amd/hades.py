@@ -95,6 +95,17 @@ class HadesMerkleTree(FieldMerkleTree):
     def _node(self, left, right):
         return self.hash.hash(left + right)[:self.digest]
 
+    _pathRootsEntry = 'gs_hades_merkle_path_roots'
+
+    @classmethod
+    def _checkDigest(cls, hash, digest):
+        if digest not in (1, 2) or 2 * digest >= hash.width:
+            raise GstarkError(f'HadesMerkleTree: nodes of {digest} elements (1 or 2): two of them do not fit a state of {hash.width} beside its capacity')
+
+    @classmethod
+    def _pathRootsOnDevice(cls, hash, paths, depth, digest, indexes, leaves, count, roots):
+        hash.field.backend.call(cls._pathRootsEntry, hash.handle(), paths, depth, digest, indexes, leaves, count, roots)
+
     @staticmethod
     def verify(root, index, proof, hash):
         """utils.ts:151-166 / :194-209 — the shape of the nodes (pairs or single integers) is the proof's"""

@@ -164,6 +164,19 @@ class RescueMerkleTree(FieldMerkleTree):
     def _node(self, left, right):
         return [self.hash.hash2(left[0], right[0])]
 
+    _pathRootsEntry, _digest = 'gs_rescue_merkle_path_roots', 1
+
+    @classmethod
+    def _checkDigest(cls, hash, digest):
+        if hash.width < 3:
+            raise GstarkError(f'RescueMerkleTree: two nodes do not fit a state of {hash.width} beside its capacity (width 3 .. 8)')
+        if digest != 1:
+            raise GstarkError(f'RescueMerkleTree: nodes of one element, not {digest}')
+
+    @classmethod
+    def _pathRootsOnDevice(cls, hash, paths, depth, digest, indexes, leaves, count, roots):
+        hash.field.backend.call(cls._pathRootsEntry, hash.handle(), paths, depth, indexes, leaves, count, roots)
+
     @staticmethod
     def verify(root, index, proof, hash2):
         """utils.ts:257-272"""

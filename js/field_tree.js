@@ -2,7 +2,8 @@
 // js/field_tree.js — what js/hades.js and js/rescue.js share above the addon's table: a device handle made on first use and destroyed
 // when its owner is collected, one permutation per row of a device Matrix, and the heap-layout Merkle tree of nodes of `digest` field
 // elements with its paths (the gather is the family-neutral gs_hades_merkle_paths: it reads nothing but the node array) and its batched
-// updates (include/gstark_tree_update.h: update / updateMany return every update's witness).
+// updates (include/gstark_tree_update.h: update / updateMany return every update's witness), and the consuming side of both
+// (include/gstark_tree_verify.h: static pathRoots / verifyMany / verifyUpdates check batches of paths and update records in one launch).
 const { Matrix, Vector } = require('./galois.js');
 
 /** a registry that destroys the handle of a collected owner through `symbol` (null where the engine has none) */
@@ -22,6 +23,13 @@ function needDevice(field, family, what) {
 function needUpdate(field, symbol) {
     if (!field.lib.has || !field.lib.has(symbol)) {
         throw new Error(`the library of the field of ${field.modulus} elements has no ${symbol} entry point (include/gstark_tree_update.h): trees are not updated on this device library`);
+    }
+}
+
+/** throws when the field's library lacks `symbol` of include/gstark_tree_verify.h (optional in the same way) */
+function needVerify(field, symbol) {
+    if (!field.lib.has || !field.lib.has(symbol)) {
+        throw new Error(`the library of the field of ${field.modulus} elements has no ${symbol} entry point (include/gstark_tree_verify.h): batches of paths are not checked on this device library`);
     }
 }
 
@@ -105,4 +113,69 @@ function verifyPath(root, index, proof, node, same = (a, b) => a === b) {
     return same(root, v);
 }
 
-module.exports = { destroyRegistry, needDevice, needUpdate, lazyHandle, hashMany, DeviceTree, verifyPath };
+/** The static members pathRoots / verifyMany / verifyUpdates of a tree class (include/gstark_tree_verify.h): a verifier holds a root and
+ *  the hash object, not a tree.  family: { digest, symbol, call(field, handle, paths, depth, indexes, leaves, count, roots) }.
+ *  proofs: paths as prove returns them (the leaf, then its siblings bottom-up), or a device Matrix of one row of (depth + 1) * digest
+ *  elements per path; leaves (optional; an array, or a device array): path k starts from leaves[k] instead of its own leaf. */
+function installVerify(cls, family) {
+    const { digest, symbol } = family;
+    const shape = row => (digest === 1 ? row[0] : row);
+    const same = digest === 1 ? (a, b) => a === b : (a, b) => a.length === b.length && a.every((x, i) => x === b[i]);
+    const count = array => (array instanceof Vector ? array.length : array.rowCount);
+    /** the root each path implies, in the shape `root` has: ONE launch walks every level of every path */
+    cls.pathRoots = function (hash, indexes, proofs, leaves) {
+        const field = hash && hash.field;
+        if (!field || !hash.handle) throw new Error('the hash object must come from js/hades.js or js/rescue.js');
+        needVerify(field, symbol);
+        let paths = proofs;
+        if (Array.isArray(proofs)) {
+            if (proofs.length !== indexes.length) throw new Error(`${indexes.length} indexes and ${proofs.length} paths: a path is checked at one index`);
+            if (!proofs.length) return [];
+            if (proofs.some(path => path.length !== proofs[0].length)) throw new Error('the paths have unequal lengths: one call checks paths of one depth');
+            if (proofs[0].length < 2) throw new Error('a path is a leaf and at least one sibling');
+            if (proofs.some(path => path.some(node => (Array.isArray(node) ? node.length : 1) !== digest || (digest > 1) !== Array.isArray(node)))) throw new Error(`every node of a path has ${digest} element${digest > 1 ? 's' : ''}`);
+            paths = field.newMatrixFrom(digest === 1 ? proofs : proofs.map(path => [].concat(...path)));
+        } else {
+            if (!(proofs instanceof Matrix)) throw new Error('the paths are an array of paths or a device Matrix of one row per path');
+            field._own(paths);
+            if (paths.rowCount !== indexes.length) throw new Error(`${indexes.length} indexes and ${paths.rowCount} paths: a path is checked at one index`);
+            if (paths.colCount % digest || paths.colCount < 2 * digest) throw new Error(`a row of ${paths.colCount} elements is no leaf of ${digest} with at least one sibling`);
+            if (!paths.rowCount) return [];
+        }
+        const depth = paths.colCount / digest - 1, n = indexes.length;
+        for (const i of indexes) {
+            if (!(Number.isInteger(i) && i >= 0 && i < 2 ** depth)) throw new Error(`index ${i} is outside of the ${2 ** depth} leaves of a path of ${depth} siblings`);
+        }
+        let src = null;
+        if (leaves !== undefined && leaves !== null) {
+            src = leaves;
+            if (Array.isArray(leaves)) src = leaves.length ? (digest === 1 ? field.newVectorFrom(leaves) : field.newMatrixFrom(leaves)) : new Vector(field, 0);
+            field._own(src);
+            if (count(src) !== n) throw new Error(`${n} paths and ${count(src)} leaves: a path starts from one leaf`);
+            if ((src instanceof Vector ? 1 : src.colCount) !== digest) throw new Error(`the leaves have ${digest} element${digest > 1 ? 's' : ''} each`);
+        }
+        const roots = new Matrix(field, n, digest);
+        family.call(field, hash.handle(), paths, depth, indexes, src ? src.ptr : 0n, n, roots);
+        return roots.toValues().map(shape);
+    };
+    /** verify(root, indexes[k], proofs[k], ..) for every k: one boolean per path */
+    cls.verifyMany = function (root, indexes, proofs, hash) {
+        return cls.pathRoots(hash, indexes, proofs).map(r => same(r, root));
+    };
+    /** one boolean per record of updateMany(indexes, leaves) on a tree whose root was oldRoot: records[j].before at indexes[j] implies the
+     *  root before it (oldRoot, then records[j - 1].root as claimed) and the same siblings under leaves[j] imply records[j].root.  Two launches. */
+    cls.verifyUpdates = function (oldRoot, indexes, leaves, records, hash) {
+        const field = hash && hash.field;
+        if (!field || !hash.handle) throw new Error('the hash object must come from js/hades.js or js/rescue.js');
+        needVerify(field, symbol);
+        if (records.length !== indexes.length) throw new Error(`${indexes.length} indexes and ${records.length} records: an update is one of each`);
+        if (!records.length) { cls.pathRoots(hash, indexes, [], leaves); return []; }
+        if (records.some(r => r.before.length !== records[0].before.length)) throw new Error('the paths have unequal lengths: one call checks paths of one depth');
+        if (records[0].before.length < 2) throw new Error('a path is a leaf and at least one sibling');
+        const paths = field.newMatrixFrom(records.map(r => (digest === 1 ? r.before : [].concat(...r.before))));      // one upload serves both launches
+        const before = cls.pathRoots(hash, indexes, paths), after = cls.pathRoots(hash, indexes, paths, leaves);
+        return records.map((r, j) => same(before[j], j ? records[j - 1].root : oldRoot) && same(after[j], r.root));
+    };
+}
+
+module.exports = { destroyRegistry, needDevice, needUpdate, needVerify, lazyHandle, hashMany, DeviceTree, verifyPath, installVerify };

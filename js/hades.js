@@ -4,11 +4,12 @@
 // (BigInt arithmetic on the host, as upstream) which also carries .hashMany(matrix, digest) — one permutation per row in one launch —,
 // and MerkleTree / MerkleTree2 have the example's members (nodes, root, prove, static verify) plus proveMany(indexes) and update /
 // updateMany(indexes, leaves): the tree is built and updated by the device, the paths of any number of leaves and the witnesses of any
-// number of updates come back in one read-back.  `field` is a PrimeField of js/galois.js.  A field whose
+// number of updates come back in one read-back; static pathRoots / verifyMany / verifyUpdates (include/gstark_tree_verify.h) check batches
+// of paths and of update records on the device, one launch for all levels.  `field` is a PrimeField of js/galois.js.  A field whose
 // library lacks the entry points (they are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const crypto = require('crypto');
 const { Matrix, Vector } = require('./galois.js');
-const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, verifyPath } = require('./field_tree.js');
+const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, verifyPath, installVerify } = require('./field_tree.js');
 
 function constants(field, seed, count) {      // utils.ts:115-122
     const out = new Array(count);
@@ -93,6 +94,12 @@ class MerkleTree extends HadesTree {      // utils.ts:126-167: nodes of two elem
 class MerkleTree2 extends HadesTree {     // utils.ts:169-210: nodes of one element
     constructor(values, hash) { super(values, hash, 1); }
     static verify(root, index, proof, hash) { return verifyPath(root, index, proof, (left, right) => hash([left, right])[0]); }
+}
+
+// static pathRoots(hash, indexes, proofs, leaves?), verifyMany(root, indexes, proofs, hash), verifyUpdates(oldRoot, indexes, leaves, records, hash)
+for (const [cls, digest] of [[MerkleTree, 2], [MerkleTree2, 1]]) {
+    installVerify(cls, { digest, symbol: 'gs_hades_merkle_path_roots', call: (field, handle, paths, depth, indexes, leaves, count, roots) =>
+        field.lib.call('gs_hades_merkle_path_roots', field.ctx, handle, paths.ptr, depth, digest, indexes, leaves, count, roots.ptr) });
 }
 
 module.exports = { createHash, getRoundConstants, getMdsMatrix, MerkleTree, MerkleTree2 };

@@ -4,10 +4,11 @@
 // members of the example's Rescue class (unrollConstants, groupConstants, sponge, modifiedSponge: BigInt arithmetic on the host, as
 // upstream) and .hash2(v1, v2) = makeHashFunction, plus .hashMany(matrix, digest, modified, form) — one permutation per row in one
 // launch — and .merkleTree(values): the example's MerkleTree (nodes, root, prove, static verify) built by the device, with
-// proveMany(indexes) in one read-back.  `field` is a PrimeField of js/galois.js.  A field whose library lacks the entry points (they
+// proveMany(indexes) in one read-back and static pathRoots / verifyMany / verifyUpdates over the rescue object (include/gstark_tree_verify.h:
+// batches of paths and of update records checked on the device).  `field` is a PrimeField of js/galois.js.  A field whose library lacks the entry points (they
 // are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const { Vector } = require('./galois.js');
-const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, verifyPath } = require('./field_tree.js');
+const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, verifyPath, installVerify } = require('./field_tree.js');
 
 const registry = destroyRegistry('gs_rescue_destroy');
 const needDevice = field => needDeviceOf(field, 'rescue', 'Rescue');
@@ -117,5 +118,9 @@ class MerkleTree extends DeviceTree {      // utils.ts:232-273, built by the dev
     /** hash: a function of two values (rescue.hash2) */
     static verify(root, index, proof, hash) { return verifyPath(root, index, proof, hash); }
 }
+
+// static pathRoots(rescue, indexes, proofs, leaves?), verifyMany(root, indexes, proofs, rescue), verifyUpdates(oldRoot, indexes, leaves, records, rescue)
+installVerify(MerkleTree, { digest: 1, symbol: 'gs_rescue_merkle_path_roots', call: (field, handle, paths, depth, indexes, leaves, count, roots) =>
+    field.lib.call('gs_rescue_merkle_path_roots', field.ctx, handle, paths.ptr, depth, indexes, leaves, count, roots.ptr) });
 
 module.exports = { createRescue, MerkleTree };

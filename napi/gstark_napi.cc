@@ -131,6 +131,9 @@ const FnDesc kFns[] = {
     // include/gstark_tree_update.h: OPTIONAL in the same way; the handles are those of gs_hades_create / gs_rescue_create
     {"gs_hades_merkle_update", "cppuixpupp"},
     {"gs_rescue_merkle_update", "cppuxpupp"},
+    // include/gstark_tree_verify.h: OPTIONAL in the same way; `leaves` may be 0 (a path then starts from its own leaf)
+    {"gs_hades_merkle_path_roots", "cppiixpup"},
+    {"gs_rescue_merkle_path_roots", "cppixpup"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
