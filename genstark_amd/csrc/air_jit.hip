@@ -89,6 +89,15 @@ static void jit_join_builders() {
 }
 __attribute__((destructor)) static void jit_library_unload() { jit_join_builders(); }          // dlclose, or exit before the dependencies' finalisers
 
+// the read-only element arrays of a generated kernel: plain pointers, or (multi-limb flavours) gs_elts over the renamed argument
+#if defined(GS_WIDE_BITS)
+#define GS_ARG(name) #name "_"
+#define GS_WRAP1(name) "    const gs_elts " name " = {" name "_};\n"
+#else
+#define GS_ARG(name) #name
+#define GS_WRAP1(name) ""
+#endif
+#define GS_WRAP3(a, b, c) GS_WRAP1(a) GS_WRAP1(b) GS_WRAP1(c)
 static std::string jit_preamble() {
     std::string s;
 #if defined(GS_SMALL_Q)
@@ -104,13 +113,29 @@ static std::string jit_preamble() {
     // the straight-line products: a call in the multi-limb fields (a product is ~400 instructions there; inlining a hundred of
     // them costs minutes of compilation and buys nothing), inlined in the others
 #if defined(GS_WIDE_BITS)
-    s += "static __device__ __noinline__ fe gs_mul(const fe &a, const fe &b) { return fe_mul(a, b); }\n";
+    // A field narrower than its storage (224 bits in eight limbs: GF_NL = 7): the products read seven limbs of an element, the sums and
+    // the stores eight, so the top limb of a value is live only here and there.  hipcc (ROCm 7.2) then spills such an element as 16 + 12
+    // bytes and has been seen to store the 16-byte tuple of the upper half again after the 12-byte reload: 33 trace registers came back
+    // with limb 7 of register 0 holding its limb 3.  Every element the generated code loads or computes therefore has its unused limbs
+    // set to the constant they hold by definition (gs_top0): they are no values any more, nothing of them is kept, spilled or reloaded.
+    s += "__device__ __forceinline__ fe gs_top0(fe x) {\n"
+         "#pragma unroll\n"
+         "    for (int i = GF_NL; i < GF_LIMBS; i++) x.w[i] = 0u;\n"
+         "    return x;\n"
+         "}\n"
+         "struct gs_elts {      // an array of elements in memory, read through gs_top0\n"
+         "    const fe *p;\n"
+         "    __device__ __forceinline__ fe operator[](unsigned long long i) const { return gs_top0(p[i]); }\n"
+         "};\n"
+         "static __device__ __noinline__ fe gs_mul_call(const fe &a, const fe &b) { return fe_mul(a, b); }\n"
+         "__device__ __forceinline__ fe gs_mul(const fe &a, const fe &b) { return gs_top0(gs_mul_call(a, b)); }\n"
+         "__device__ __forceinline__ fe gs_sqr(const fe &a) { return gs_top0(gs_mul_call(a, a)); }\n"
+         "__device__ __forceinline__ fe gs_add(const fe &a, const fe &b) { return gs_top0(fe_add(a, b)); }\n"
+         "__device__ __forceinline__ fe gs_sub(const fe &a, const fe &b) { return gs_top0(fe_sub(a, b)); }\n"
+         "#define fe_add gs_add\n"
+         "#define fe_sub gs_sub\n";
 #else
     s += "#define gs_mul fe_mul\n";
-#endif
-#if defined(GS_WIDE_BITS)
-    s += "static __device__ __noinline__ fe gs_sqr(const fe &a) { return fe_mul(a, a); }\n";
-#else
     s += "#define gs_sqr fe_sqr\n";
 #endif
     // c ? a : b limb by limb: written as a conditional copy of the struct, the compiler parks the candidates in scratch memory and
@@ -553,6 +578,7 @@ static void ssa_fuse_dots(std::vector<SsaNode> &nodes) {
 static bool ssa_build(std::vector<SsaNode> &nodes, const JitGen &gen, const uint32_t *code, uint32_t ninstr, uint32_t vm_regs, bool allow_statics,
                       bool allow_next = false) {
     std::vector<int> cur(vm_regs, -1);
+    std::map<uint32_t, int> last_out;      // destination -> its latest OUT node (the machine is sequential: the last write wins)
     auto add = [&](SsaNode n) { nodes.push_back(n); return (int)nodes.size() - 1; };
     auto use = [&](uint32_t r) {
         if (cur[r] < 0) { SsaNode z; cur[r] = add(z); }
@@ -626,7 +652,10 @@ static bool ssa_build(std::vector<SsaNode> &nodes, const JitGen &gen, const uint
             case J_OUT:
                 if (a >= vm_regs) return false;
                 n.kind = SsaNode::OUT; n.a = use(a); n.aux = d; n.depth = nodes[n.a].depth;
-                add(n);
+                // outputs are emitted depth by depth, not in program order: an earlier OUT to the same destination is dropped here,
+                // or it would overwrite this one whenever its value is the deeper of the two
+                if (last_out.count(d)) nodes[last_out[d]].kind = SsaNode::DEAD;
+                last_out[d] = add(n);
                 break;
             default: return false;      // J_LOADN does not occur in trace programs
         }
@@ -1194,8 +1223,9 @@ static bool jit_trace_source(std::string &s, JitGen &gen, const uint32_t *code, 
     ssa_align_pows(init_nodes);
     gen.lanes = std::max(ssa_lanes(main_nodes), ssa_lanes(init_nodes));
     snprintf(buf, sizeof buf, "#define GS_LANES %uu\n", gen.lanes); s += buf;
-    s += "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void gs_jit_trace(const fe *__restrict__ consts, const fe *__restrict__ statics, const fe *__restrict__ first_rows,\n"
+    s += "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void gs_jit_trace(const fe *__restrict__ " GS_ARG(consts) ", const fe *__restrict__ " GS_ARG(statics) ", const fe *__restrict__ " GS_ARG(first_rows) ",\n"
          "                                         unsigned long long segments, unsigned long long seglen, fe *__restrict__ out) {\n"
+         GS_WRAP3("consts", "statics", "first_rows")
          "    const unsigned long long tid = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x;\n"
          "    // every thread runs every step (and reaches every barrier): the lanes past the last segment recompute it and store nothing\n"
          "    const bool gs_live = tid / GS_LANES < segments;\n"
@@ -1332,9 +1362,10 @@ static bool jit_constraints_source(std::string &s, const JitGen &gen, const uint
     char buf[256];
     // register r at point j is p[r * prow + j * pstride]: the columns may be those of a larger domain read with a stride (the composition
     // domain inside the evaluation domain: gs_air_constraints_strided) — no plucked copy of the trace extension
-    s += "extern \"C\" __global__ __launch_bounds__(128) void gs_jit_constraints(const fe *__restrict__ consts, const fe *__restrict__ p, unsigned long long nc,\n"
-         "                                               unsigned long long shift, const fe *__restrict__ statics, fe *__restrict__ out,\n"
-         "                                               unsigned long long prow, unsigned long long pstride) {\n";
+    s += "extern \"C\" __global__ __launch_bounds__(128) void gs_jit_constraints(const fe *__restrict__ " GS_ARG(consts) ", const fe *__restrict__ " GS_ARG(p) ", unsigned long long nc,\n"
+         "                                               unsigned long long shift, const fe *__restrict__ " GS_ARG(statics) ", fe *__restrict__ out,\n"
+         "                                               unsigned long long prow, unsigned long long pstride) {\n"
+         GS_WRAP3("consts", "p", "statics");
     for (uint32_t t = 0; t < vm_regs; t++) { snprintf(buf, sizeof buf, "    fe t%u;\n", t); s += buf; }
     s += "    for (unsigned long long j = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; j < nc; j += (unsigned long long)gridDim.x * blockDim.x) {\n"
          "        unsigned long long jn = j + shift;\n"

@@ -1,7 +1,8 @@
 """The code generator of csrc/air_jit.hip, checked where there is no GPU: gs_air_jit_check turns an AIR program into HIP source and
 runs the compiler (hiprtc cross-compiles gfx950 without a device) — the "does it build" tier for what a serving prover compiles at
 run time.  The values the compiled programs compute are compared with the interpreter's in the gpu tier
-(test_generic_air.py::test_compiled_air_programs_equal_interpreted, test_pipeline.py)."""
+(test_generic_air.py::test_compiled_air_programs_equal_interpreted, test_pipeline.py; test_air_programs.py for programs written for
+every branch of the generator)."""
 import ctypes as C
 import os
 
@@ -11,6 +12,7 @@ from genstark_amd import lib224, poseidon
 from genstark_amd._abi import GS_OK, HIP_LIB_PATHS, MODULUS_128, MODULUS_224, load_library
 from genstark_amd.pointmul import point_mul_air
 from genstark_amd.field import PrimeField
+from air_programs import chain_exponent
 from test_generic_air import rescue4x128_air
 from test_wide_fields import oracle_for
 
@@ -183,34 +185,6 @@ def test_background_builds_run_in_the_helper_process(tmp_path):
     r = subprocess.run([sys.executable, '-c', HELPER_SCRIPT, _abi.HIP_LIB_PATH, str(tmp_path / 'none.hsaco'), 'lazy'],
                        env=dict(os.environ, GSTARK_JITC=str(tmp_path / 'no_such_helper')), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'GOOD -1' in r.stdout, r.stdout + r.stderr[-1000:]
-
-
-def chain_exponent(block):
-    """The exponent a generated lazy-form chain computes, by following its statements with integers (x = p1 has exponent 1)."""
-    import re
-    val = {'p1': 1}
-    lines = block.split('\n')
-    i = 0
-    while i < len(lines):
-        ln = lines[i].strip()
-        i += 1
-        m = re.match(r'for \(int q = 0; q < (\d+); q\+\+\) (\w+) = lz_sqr\((\w+), K\);', ln)
-        if m:
-            assert m.group(2) == m.group(3)
-            val[m.group(2)] <<= int(m.group(1))
-            continue
-        m = re.match(r'(?:const lz |lz )?(\w+) = lz_sqr\((\w+), K\);', ln)
-        if m:
-            val[m.group(1)] = 2 * val[m.group(2)]
-            continue
-        m = re.match(r'(?:const lz |lz )?(\w+) = lz_mul_v\((\w+), (\w+), K\);', ln)
-        if m:
-            val[m.group(1)] = val[m.group(2)] + val[m.group(3)]
-            continue
-        m = re.match(r'(?:const lz |lz )?(\w+) = (\w+);$', ln)
-        if m and m.group(2) in val:
-            val[m.group(1)] = val[m.group(2)]
-    return val['acc'], sum(1 for l in lines if 'lz_mul_v(' in l), val
 
 
 def test_inverse_sbox_chain_uses_the_periodic_pattern(oracle_backend, hip_libs, tmp_path, monkeypatch):
