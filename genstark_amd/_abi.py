@@ -178,6 +178,15 @@ _TREE_VERIFY_SIGNATURES = {
 }
 TREE_VERIFY_SYMBOLS = tuple(_TREE_VERIFY_SIGNATURES)
 
+# include/gstark_mimc.h: gs_mimc_composition from per-point tables built before the trace; optional in the same way (a driver bound to a
+# library without them calls gs_mimc_composition)
+_MIMC_SIGNATURES = {
+    'gs_mimc_composition_prepare': (_int, [_vp, _u64, _u64, _bytes, C.POINTER(_u64), _u32, _bytes]),
+    'gs_mimc_composition_tables': _SIGNATURES['gs_mimc_composition'],
+    'gs_mimc_composition_tables_max_n': (_u64, [_u64]),
+}
+MIMC_SYMBOLS = tuple(_MIMC_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -193,7 +202,7 @@ def load_library(path):
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
-                              + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items())):
+                              + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -75,6 +75,14 @@ struct gs_ctx {
     // host-side scalar tables that depend on the domain alone (1 / (g^j - 1), powers of omega by fixed exponents): a proof server asks
     // for the same ones with every proof, and an inversion is 4 us of host time on the critical path of a 0.5 ms proof (gs_memo)
     std::map<std::string, std::vector<fe>> scalar_memo;
+    // per-point factors of the MiMC composition pass over one evaluation domain (gs_mimc_composition_prepare, air_mimc.hip): n elements
+    // each.  X and U are kept from proof to proof under the key of what they depend on, IU is rebuilt by every prepare; one shape per
+    // context (a service proves one statement shape on one domain), another shape replaces them
+    struct MimcTables {
+        fe *X = nullptr, *U = nullptr, *IU = nullptr;
+        uint64_t n = 0;
+        std::string x_key, u_key, iu_key;       // empty: not built
+    } mimc_tables;
     uint64_t jit_launches = 0;    // compiled-program launches so far (gs_air_jit_launches)
     // gs_traffic_enable / gs_traffic_read: per kernel name {launches, algorithmic bytes, work units} of the launches issued while on
     bool traffic_on = false;

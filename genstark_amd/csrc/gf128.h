@@ -154,9 +154,12 @@ GF_HD uint32_t gf_fsh(uint32_t hi, uint32_t lo, int s) { return (hi << s) | (lo 
 //     =: V = (v0..v3) + T*2^128,  T = (v4, v5) < 2^37, V >= 0
 //     == (v0..v3) + T*(9*2^32 - 1)                    (second fold, T*C < 2^74)
 //     =: w + k*2^128, k in {0,1}; k = 1 leaves w tiny, so a single "+C / conditional -p" finishes.
-GF_HD fe fe_reduce_wide(const uint32_t r[8]) {
+// fe_reduce_wide9: the same for x + r8*2^256, r8 < 2^24 — a sum of a few products (fe_wide_add) reduced ONCE.  hi then has a fifth
+// limb: A = 9*hi < 2^156 still ends at a4 (< 2^28), T = (v4, v5) < 2^60 and T*C < 2^96 still fills three limbs, so only A's last mad
+// and V's fifth limb see r8; with r8 = 0 both drop out again.
+GF_HD fe fe_reduce_wide9(const uint32_t r[8], uint32_t r8) {
     uint32_t c, b;
-    // A = 9*hi, limbs a0..a4 (a4 < 9): four chained mads instead of shift + carry-add pairs
+    // A = 9*hi, limbs a0..a4 (a4 < 9 + 9*r8): chained mads instead of shift + carry-add pairs
     uint64_t m = (uint64_t)r[4] * 9u;
     uint32_t a0 = (uint32_t)m;
     m = (uint64_t)r[5] * 9u + (m >> 32);
@@ -164,7 +167,9 @@ GF_HD fe fe_reduce_wide(const uint32_t r[8]) {
     m = (uint64_t)r[6] * 9u + (m >> 32);
     uint32_t a2 = (uint32_t)m;
     m = (uint64_t)r[7] * 9u + (m >> 32);
-    uint32_t a3 = (uint32_t)m, a4 = (uint32_t)(m >> 32);
+    uint32_t a3 = (uint32_t)m;
+    m = (uint64_t)r8 * 9u + (m >> 32);
+    uint32_t a4 = (uint32_t)m;
     // U = lo + (A << 32), six limbs
     uint32_t u1 = gf_addc(r[1], a0, 0u, c);
     uint32_t u2 = gf_addc(r[2], a1, c, c);
@@ -176,7 +181,7 @@ GF_HD fe fe_reduce_wide(const uint32_t r[8]) {
     uint32_t v1 = gf_subc(u1, r[5], b, b);
     uint32_t v2 = gf_subc(u2, r[6], b, b);
     uint32_t v3 = gf_subc(u3, r[7], b, b);
-    uint32_t t0 = gf_subc(u4, 0u, b, b);
+    uint32_t t0 = gf_subc(u4, r8, b, b);
     uint32_t t1 = u5 - b;
     // G = 9*T (two limbs), E = T*C = (G << 32) - T (three limbs, >= 0)
     uint32_t g0 = gf_addc(t0 << 3, t0, 0u, c);
@@ -204,6 +209,15 @@ GF_HD fe fe_reduce_wide(const uint32_t r[8]) {
     o.w2 = sel ? t.w2 : w.w2;
     o.w3 = sel ? t.w3 : w.w3;
     return o;
+}
+GF_HD fe fe_reduce_wide(const uint32_t r[8]) { return fe_reduce_wide9(r, 0u); }
+// x += y over 256 bits, the carry out of them added to `top`: the ninth limb of a sum of products, for fe_reduce_wide9
+GF_HD void fe_wide_add(uint32_t x[8], const uint32_t y[8], uint32_t &top) {
+    uint32_t c;
+    x[0] = gf_addc(x[0], y[0], 0u, c);
+#pragma unroll
+    for (int i = 1; i < 8; i++) x[i] = gf_addc(x[i], y[i], c, c);
+    top += c;
 }
 
 GF_HD fe fe_mul(const fe &a, const fe &b) {

@@ -26,6 +26,7 @@
 #include "../../include/gstark_prover.h"
 #include "../../include/gstark_comm.h"
 #include "../../include/gstark_boundary.h"
+#include "../../include/gstark_mimc.h"
 // One build of this file per field flavour of the ABI library (csrc/build.sh: the same -DGS_SMALL_Q / -DGS_WIDE_BITS): the host-side
 // scalars (domain roots, Fiat-Shamir coefficients, boundary interpolants, the remainder check) use the flavour's host arithmetic,
 // elements are gs_element_size() bytes on the ABI and in the proof.
@@ -48,7 +49,8 @@ namespace {
     X(gs_air_trace_segments) X(gs_air_constraints) X(gs_air_constraints_strided) X(gs_composition_tail) X(gs_composition_tail_coset) X(gs_zero_poly_inverses) X(gs_div_by_domain_roots) X(gs_mimc_composition) X(gs_fri_fold) X(gs_fri_fold_seeded) X(gs_defer_begin) X(gs_defer_end) X(gs_readback_post) X(gs_readback_wait) X(gs_merkle_commit_rows_seed) X(gs_fri_fold_at) \
     X(gs_vec_mul_scalar) X(gs_copy) X(gs_gather_words) X(gs_transpose_records) X(gs_fri_fold_seeded_scaled) X(gs_fri_layers) X(gs_sync) X(gs_zero_poly_inverses_coset) X(gs_div_by_domain_roots_coset)
 // ... and the entry points an implementation may lack (include/gstark_boundary.h): null then, and the driver keeps its host path
-#define GS_API_OPTIONAL_LIST(X) X(gs_boundary_polys) X(gs_eval_polys_at_points)
+// (include/gstark_mimc.h: without them the fused MiMC branch calls gs_mimc_composition)
+#define GS_API_OPTIONAL_LIST(X) X(gs_boundary_polys) X(gs_eval_polys_at_points) X(gs_mimc_composition_prepare) X(gs_mimc_composition_tables)
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
     GS_API_LIST(X)
@@ -1138,6 +1140,25 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         x.check(counted_eval_polys_at_roots(x.c, kPoly.p, 1, air.k_len, enc(hf_pow(omega, (hfe)(N / klen_n))), klen_n, kN.p), "gs_eval_polys_at_roots(K)");
     }
 
+    // MiMC, fused: the per-point factors of the composition pass that need neither the trace nor a coefficient — the domain points, the
+    // interpolant through the assertions, the divisions by (x - x_a) — are tabulated now, while the device has nothing else to do
+    // (include/gstark_mimc.h), where the bound library has the entry points; it answers GS_OK also when it declines to make the
+    // tables and its composition call then runs gs_mimc_composition.  Assertions the checks below will refuse are left to them
+    Plan::Boundary fused_bd;
+    bool comp_tables = false;
+    if (fused && A.gs_mimc_composition_prepare && A.gs_mimc_composition_tables) {
+        const std::vector<uint64_t> &at = plan.regs[0].steps;
+        bool sound = true;
+        for (size_t i = 0; i < at.size(); i++) {
+            if (at[i] >= T) sound = false;
+            for (size_t k = 0; k < i; k++) if (at[k] == at[i]) sound = false;
+        }
+        if (sound) {
+            fused_bd = plan.boundary(E, true);
+            comp_tables = A.gs_mimc_composition_prepare(x.c, N, T, enc(omega), fused_bd.at.data(), fused_bd.per_row[0], fused_bd.interpolants.data()) == GS_OK;
+        }
+    }
+
     clock.mark("context + trace-independent work issued");
     clock.readme(x, "Set up evaluation context");
     // 2 ----- execution trace (:97) and the assertions it must satisfy (:356-375)
@@ -1189,7 +1210,7 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
     if (fused) {
         // K over the evaluation domain (issued before the trace), the interpolant through the assertions (all on register 0: one row
         // of the boundary plan), then one kernel for :71-146 (what needs no coefficient first: the device is idle while the root travels)
-        const Plan::Boundary bd = plan.boundary(E, true);
+        const Plan::Boundary bd = comp_tables ? std::move(fused_bd) : plan.boundary(E, true);
         read_evaluation_root();
         const bool q_adjusted = plan.groups[0].first < combination_degree;
         Bytes co(4 * ELEM, 0);
@@ -1201,8 +1222,10 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
         lc_fused = lc_folds;
         Bytes lc = lc_folds ? pack(coefficients, dcount + bcoef, plan.lccount(V)) : Bytes();
         lc.resize(2 * ELEM, 0);                                    // (the kernel reads two; the second is 0 without a degree adjustment)
-        x.check(A.gs_mimc_composition(x.c, pRows[0], N, T, enc(omega), kN.p, klen_n, co.data(), q_adjusted ? combination_degree - plan.groups[0].first : 0, b_inc,
-                                      bd.interpolants.data(), bd.at.data(), bd.per_row[0], lc_folds ? lc.data() : nullptr, cEval.p), "gs_mimc_composition");
+        const auto composition = comp_tables ? A.gs_mimc_composition_tables : A.gs_mimc_composition;      // (same arguments, same values)
+        x.check(composition(x.c, pRows[0], N, T, enc(omega), kN.p, klen_n, co.data(), q_adjusted ? combination_degree - plan.groups[0].first : 0, b_inc,
+                            bd.interpolants.data(), bd.at.data(), bd.per_row[0], lc_folds ? lc.data() : nullptr, cEval.p),
+                comp_tables ? "gs_mimc_composition_tables" : "gs_mimc_composition");
     } else {
         // 5.1-5.3: the combined, degree-adjusted Q has degree < Nc, so its extension to the evaluation domain (:109-110) is what
         // the constraint expression gives there.  MiMC (one cheap constraint): evaluate it on all N points from the extension of P

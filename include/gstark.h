@@ -328,7 +328,8 @@ int gs_mimc_constraints(gs_ctx *ctx, const void *p_comp, uint64_t nc, uint64_t s
  *            = C + p[i] * (l0 + l1 * x^b_inc)     otherwise: LinearCombination.computeMany for one register, no secret registers
  *                                                 (LinearCombination.ts:36-64; same degree increment, same prng stream)
  * coeffs_host = d0, d1, b0, b1; lc_coeffs_host = l0, l1; q_inc, b_inc multiples of steps; n/steps <= 32; 1 <= nroots <= 4 (GS_ERR_UNSUPPORTED otherwise:
- * the member-by-member sequence gives the same values). */
+ * the member-by-member sequence gives the same values).
+ * include/gstark_mimc.h has an optional pair of entry points that gives the same output from per-point tables built before the trace. */
 int gs_mimc_composition(gs_ctx *ctx, const void *p_eval, uint64_t n, uint64_t steps, const gs_elt *omega, const void *k_table,
                         uint64_t klen, const uint8_t *coeffs_host, uint64_t q_inc, uint64_t b_inc, const uint8_t *ipoly_host,
                         const uint64_t *root_index_host, uint32_t nroots, const uint8_t *lc_coeffs_host, void *out);
