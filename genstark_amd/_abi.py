@@ -187,6 +187,14 @@ _MIMC_SIGNATURES = {
 }
 MIMC_SYMBOLS = tuple(_MIMC_SIGNATURES)
 
+# include/gstark_curve.h: scalar multiplications on short Weierstrass curves over the field; optional in the same way
+# (genstark_amd/curve.py computes on host integers where a library lacks them)
+_CURVE_SIGNATURES = {
+    'gs_curve_mul': (_int, [_vp, _bytes, _vp, _u64, _vp, _u32, _vp, _vp, _u64, _vp, _vp]),
+    'gs_curve_contains': (_int, [_vp, _bytes, _bytes, _vp, _u64, _vp]),
+}
+CURVE_SYMBOLS = tuple(_CURVE_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -202,7 +210,8 @@ def load_library(path):
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
-                              + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())):
+                              + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
+                              + list(_CURVE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -99,6 +99,19 @@ def to_bits(value, length=STEPS):
     return [(value >> i) & 1 for i in range(length)]
 
 
+def point_mul_inputs(curve, points, scalars):
+    """(raw, assertions) for point_mul_air(curve.field, len(points)): raw = [xs, ys, bit lists] (pointMul.ts:22-26) and the assertions of
+    pointMul.ts:33-36 per multiplication s — the product in registers 2, 3 at step 256*s + 255 —, the products computed in one batch by
+    `curve.mulMany` (genstark_amd/curve.py: on the device)."""
+    points, scalars = [tuple(pt) for pt in points], [int(k) for k in scalars]
+    products = curve.mulMany(points, scalars)
+    if any(pt is None for pt in products):
+        raise ValueError('point_mul_inputs: a product is the point at infinity, which the trace cannot hold')
+    raw = [[pt[0] for pt in points], [pt[1] for pt in points], [to_bits(k) for k in scalars]]
+    assertions = [{'step': STEPS * s + STEPS - 1, 'register': 2 + i, 'value': pt[i]} for s, pt in enumerate(products) for i in range(2)]
+    return raw, assertions
+
+
 def ec_multiply(p, point, scalar):
     """Plain double-and-add on the same curve (control computation on Python integers; affine, no special cases beyond infinity)."""
     a = CURVE_A % p

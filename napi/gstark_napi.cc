@@ -134,6 +134,9 @@ const FnDesc kFns[] = {
     // include/gstark_tree_verify.h: OPTIONAL in the same way; `leaves` may be 0 (a path then starts from its own leaf)
     {"gs_hades_merkle_path_roots", "cppiixpup"},
     {"gs_rescue_merkle_path_roots", "cppixpup"},
+    // include/gstark_curve.h: OPTIONAL in the same way; `addends` and `addend_inf` may be 0 (every addend / no addend is infinity)
+    {"gs_curve_mul", "cbpupippupp"},
+    {"gs_curve_contains", "cbbpup"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
