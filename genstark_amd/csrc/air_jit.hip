@@ -33,8 +33,7 @@
 
 #include "common.h"
 #include "host_hash.h"
-
-enum { J_LOADC = 0, J_LOADR = 1, J_LOADN = 2, J_LOADS = 3, J_ADDV = 4, J_SUBV = 5, J_MULV = 6, J_POW = 7, J_POWC = 8, J_OUT = 9 };
+#include "air_program.h"
 
 static const char *kFieldHeader =
 #if defined(GS_SMALL_Q)
@@ -237,28 +236,24 @@ static std::string jit_preamble() {
     return s;
 }
 
-// What the generator knows besides the program: the constant pool (exponents become addition chains at generation time) and, in
-// the trace kernel, how many lanes work on one segment.
+// What the generator knows besides the program (an AirProgram: its constant pool is where exponents become addition chains at generation
+// time): in the trace kernel, how many lanes work on one segment, and the tables of the static registers.
 struct JitGen {
-    const uint8_t *consts = nullptr;   // host copy, nconsts x GS_ELT bytes
-    uint32_t nconsts = 0;
     uint32_t lanes = 1;                // 1, 2 or 4 consecutive lanes per segment (trace kernel only)
-    // trace programs: host copy of the static registers' tables (element soff[s] + i), or null.  A static register whose table holds
-    // only 0 and 1 is a SELECTOR (Poseidon's full / partial round flag): products by it are emitted as selects (SsaNode::BLEND)
+    // trace programs: host copy of the static registers' tables (element p.sd.offset[s] + i), or null.  A static register whose table
+    // holds only 0 and 1 is a SELECTOR (Poseidon's full / partial round flag): products by it are emitted as selects (SsaNode::BLEND)
     const uint8_t *statics = nullptr;
-    const uint64_t *soff = nullptr, *slen = nullptr;
-    uint32_t nstatic = 0;
-    bool static_is_binary(uint32_t reg) const {
+    bool static_is_binary(const AirProgram &p, uint32_t reg) const {
 #ifdef GS_FIELD_128
-        if (!statics || !soff || !slen || reg >= nstatic) return false;
-        for (uint64_t i = 0; i < slen[reg]; i++) {
-            const uint8_t *v = statics + (soff[reg] + i) * GS_ELT;
+        if (!statics || reg >= p.nstatic) return false;
+        for (uint64_t i = 0; i < p.sd.len[reg]; i++) {
+            const uint8_t *v = statics + (p.sd.offset[reg] + i) * GS_ELT;
             if (v[0] > 1) return false;
             for (int b = 1; b < GS_ELT; b++) if (v[b]) return false;
         }
-        return slen[reg] > 0;
+        return p.sd.len[reg] > 0;
 #else
-        (void)reg;
+        (void)p; (void)reg;
         return false;
 #endif
     }
@@ -429,51 +424,35 @@ static void emit_pow(std::string &s, const char *x, const std::vector<uint32_t> 
     snprintf(buf, sizeof buf, "                %s = acc;\n            }\n", x); s += buf;
 }
 
-// adjacent exponentiations with one exponent whose results do not feed each other (the S-boxes of a round)
-static uint32_t pow_group_size(const uint32_t *code, uint32_t ninstr, uint32_t pc) {
-    const uint32_t op = code[4 * pc], b = code[4 * pc + 3];
-    uint32_t g = 1;
-    while (g < 4 && pc + g < ninstr) {
-        const uint32_t *nx = code + 4 * (pc + g);
-        bool ok = nx[0] == op && nx[3] == b;
-        for (uint32_t i = 0; ok && i < g; i++) ok = nx[2] != code[4 * (pc + i) + 1];
-        if (!ok) break;
-        g++;
-    }
-    return g;
-}
-
-// straight-line statements for a constraint program (one thread per domain point: throughput-bound, no lanes); `index` names the
-// loop variable static tables are indexed by
-static bool jit_body(std::string &s, const JitGen &gen, const uint32_t *code, uint32_t ninstr, const uint64_t *soff, const uint64_t *slen,
-                     bool allow_statics, const char *cur, const char *nxt, const char *index, const char *sink) {
+// straight-line statements for `ninstr` instructions at `code` of the constraint program p (one thread per domain point:
+// throughput-bound, no lanes); `index` names the loop variable static tables are indexed by
+static bool jit_body(std::string &s, const AirProgram &p, const uint32_t *code, uint32_t ninstr, bool allow_statics, const char *cur, const char *nxt,
+                     const char *index, const char *sink) {
     char buf[256];
+    const uint64_t *soff = p.sd.offset, *slen = p.sd.len;
     for (uint32_t pc = 0; pc < ninstr; pc++) {
         const uint32_t op = code[4 * pc], d = code[4 * pc + 1], a = code[4 * pc + 2], b = code[4 * pc + 3];
         switch (op) {
-            case J_LOADC: snprintf(buf, sizeof buf, "        t%u = consts[%u];\n", d, a); break;
-            case J_LOADR: snprintf(buf, sizeof buf, "        t%u = %s%u;\n", d, cur, a); break;
-            case J_LOADN:
+            case OP_LOADC: snprintf(buf, sizeof buf, "        t%u = consts[%u];\n", d, a); break;
+            case OP_LOADR: snprintf(buf, sizeof buf, "        t%u = %s%u;\n", d, cur, a); break;
+            case OP_LOADN:
                 if (!nxt) return false;
                 snprintf(buf, sizeof buf, "        t%u = %s%u;\n", d, nxt, a);
                 break;
-            case J_LOADS:
+            case OP_LOADS:
                 if (!allow_statics) return false;
                 if (slen[a] & (slen[a] - 1)) snprintf(buf, sizeof buf, "        t%u = statics[%lluull + %s %% %lluull];\n", d, (unsigned long long)soff[a], index, (unsigned long long)slen[a]);
                 else snprintf(buf, sizeof buf, "        t%u = statics[%lluull + (%s & %lluull)];\n", d, (unsigned long long)soff[a], index, (unsigned long long)(slen[a] - 1));
                 break;
-            case J_ADDV: snprintf(buf, sizeof buf, "        t%u = fe_add(t%u, t%u);\n", d, a, b); break;
-            case J_SUBV: snprintf(buf, sizeof buf, "        t%u = fe_sub(t%u, t%u);\n", d, a, b); break;
-            case J_MULV: snprintf(buf, sizeof buf, "        t%u = gs_mul(t%u, t%u);\n", d, a, b); break;
-            case J_POW:
-            case J_POWC: {
+            case OP_ADDV: snprintf(buf, sizeof buf, "        t%u = fe_add(t%u, t%u);\n", d, a, b); break;
+            case OP_SUBV: snprintf(buf, sizeof buf, "        t%u = fe_sub(t%u, t%u);\n", d, a, b); break;
+            case OP_MULV: snprintf(buf, sizeof buf, "        t%u = gs_mul(t%u, t%u);\n", d, a, b); break;
+            case OP_POW:
+            case OP_POWC: {
                 std::vector<uint32_t> e(GS_ELT / 4, 0u);
-                if (op == J_POW) e[0] = b;
-                else {
-                    if (!gen.consts || b >= gen.nconsts) return false;
-                    memcpy(e.data(), gen.consts + (size_t)b * GS_ELT, GS_ELT);
-                }
-                const uint32_t g = pow_group_size(code, ninstr, pc);
+                if (op == OP_POW) e[0] = b;
+                else memcpy(e.data(), p.consts + (size_t)b * GS_ELT, GS_ELT);
+                const uint32_t g = air_pow_group(code, ninstr, pc);
                 s += "        {\n";
                 for (uint32_t i = 0; i < g; i++) { snprintf(buf, sizeof buf, "            fe x%u = t%u;\n", i, code[4 * (pc + i) + 2]); s += buf; }
                 for (uint32_t i = 0; i < g; i++) { snprintf(buf, sizeof buf, "x%u", i); emit_pow(s, std::string(buf).c_str(), e); }
@@ -482,7 +461,7 @@ static bool jit_body(std::string &s, const JitGen &gen, const uint32_t *code, ui
                 pc += g - 1;
                 break;
             }
-            case J_OUT: snprintf(buf, sizeof buf, "        %s%u = t%u;\n", sink, d, a); break;
+            case OP_OUT: snprintf(buf, sizeof buf, "        %s%u = t%u;\n", sink, d, a); break;
             default: return false;
         }
         s += buf;
@@ -575,9 +554,9 @@ static void ssa_fuse_dots(std::vector<SsaNode> &nodes) {
     ssa_recompute_depths(nodes);
 }
 
-static bool ssa_build(std::vector<SsaNode> &nodes, const JitGen &gen, const uint32_t *code, uint32_t ninstr, uint32_t vm_regs, bool allow_statics,
-                      bool allow_next = false) {
-    std::vector<int> cur(vm_regs, -1);
+// false: the program has something this route does not generate code for (what is ill-formed the validator has refused before)
+static bool ssa_build(std::vector<SsaNode> &nodes, const JitGen &gen, const AirProgram &p, bool allow_statics, bool allow_next = false) {
+    std::vector<int> cur(p.vm_regs, -1);
     std::map<uint32_t, int> last_out;      // destination -> its latest OUT node (the machine is sequential: the last write wins)
     auto add = [&](SsaNode n) { nodes.push_back(n); return (int)nodes.size() - 1; };
     auto use = [&](uint32_t r) {
@@ -590,29 +569,27 @@ static bool ssa_build(std::vector<SsaNode> &nodes, const JitGen &gen, const uint
         n.depth = std::max(nodes[x].depth, nodes[y].depth) + (k == SsaNode::MUL ? 1 : 0);
         return add(n);
     };
-    for (uint32_t pc = 0; pc < ninstr; pc++) {
-        const uint32_t op = code[4 * pc], d = code[4 * pc + 1], a = code[4 * pc + 2], b = code[4 * pc + 3];
-        if (op != J_OUT && d >= vm_regs) return false;
+    for (uint32_t pc = 0; pc < p.ninstr; pc++) {
+        const uint32_t op = p.code[4 * pc], d = p.code[4 * pc + 1], a = p.code[4 * pc + 2], b = p.code[4 * pc + 3];
         SsaNode n;
         switch (op) {
-            case J_LOADC: n.kind = SsaNode::CONSTV; n.a = (int)a; cur[d] = add(n); break;
-            case J_LOADR: n.kind = SsaNode::ROW; n.a = (int)a; cur[d] = add(n); break;
-            case J_LOADN:
+            case OP_LOADC: n.kind = SsaNode::CONSTV; n.a = (int)a; cur[d] = add(n); break;
+            case OP_LOADR: n.kind = SsaNode::ROW; n.a = (int)a; cur[d] = add(n); break;
+            case OP_LOADN:
                 if (!allow_next) return false;       // (does not occur in trace programs)
                 n.kind = SsaNode::ROWN; n.a = (int)a; cur[d] = add(n);
                 break;
-            case J_LOADS:
+            case OP_LOADS:
                 if (!allow_statics) return false;
                 n.kind = SsaNode::STATICV; n.a = (int)a; cur[d] = add(n);
                 break;
-            case J_ADDV: case J_SUBV: case J_MULV: {
-                if (a >= vm_regs || b >= vm_regs) return false;
+            case OP_ADDV: case OP_SUBV: case OP_MULV: {
                 const int x = use(a), y = use(b);
-                if (op == J_MULV) {
+                if (op == OP_MULV) {
                     // a product by a 0/1 selector is a select: cheap, on every lane, no round of its own (gs_blend still multiplies
                     // should the table ever hold anything else)
-                    const bool fx = nodes[x].kind == SsaNode::STATICV && gen.static_is_binary((uint32_t)nodes[x].a);
-                    const bool fy = nodes[y].kind == SsaNode::STATICV && gen.static_is_binary((uint32_t)nodes[y].a);
+                    const bool fx = nodes[x].kind == SsaNode::STATICV && gen.static_is_binary(p, (uint32_t)nodes[x].a);
+                    const bool fy = nodes[y].kind == SsaNode::STATICV && gen.static_is_binary(p, (uint32_t)nodes[y].a);
                     if (fx || fy) {
                         SsaNode bl;
                         bl.kind = SsaNode::BLEND; bl.a = fx ? x : y; bl.b = fx ? y : x;
@@ -621,16 +598,14 @@ static bool ssa_build(std::vector<SsaNode> &nodes, const JitGen &gen, const uint
                         break;
                     }
                 }
-                cur[d] = binary(op == J_ADDV ? SsaNode::ADD : (op == J_SUBV ? SsaNode::SUB : SsaNode::MUL), x, y);
+                cur[d] = binary(op == OP_ADDV ? SsaNode::ADD : (op == OP_SUBV ? SsaNode::SUB : SsaNode::MUL), x, y);
                 break;
             }
-            case J_POW: case J_POWC: {
-                if (a >= vm_regs) return false;
+            case OP_POW: case OP_POWC: {
                 const int x = use(a);
                 uint64_t e = b;
-                if (op == J_POWC) {
-                    if (!gen.consts || b >= gen.nconsts) return false;
-                    const uint8_t *eb = gen.consts + (size_t)b * GS_ELT;
+                if (op == OP_POWC) {
+                    const uint8_t *eb = p.consts + (size_t)b * GS_ELT;
                     bool wide_exponent = false;
                     for (int i = 4; i < GS_ELT; i++) wide_exponent |= eb[i] != 0;
                     if (wide_exponent) {
@@ -649,15 +624,14 @@ static bool ssa_build(std::vector<SsaNode> &nodes, const JitGen &gen, const uint
                 cur[d] = add(n);
                 break;
             }
-            case J_OUT:
-                if (a >= vm_regs) return false;
+            case OP_OUT:
                 n.kind = SsaNode::OUT; n.a = use(a); n.aux = d; n.depth = nodes[n.a].depth;
                 // outputs are emitted depth by depth, not in program order: an earlier OUT to the same destination is dropped here,
                 // or it would overwrite this one whenever its value is the deeper of the two
                 if (last_out.count(d)) nodes[last_out[d]].kind = SsaNode::DEAD;
                 last_out[d] = add(n);
                 break;
-            default: return false;      // J_LOADN does not occur in trace programs
+            default: return false;      // OP_LOADN does not occur in trace programs
         }
     }
     return true;
@@ -725,10 +699,10 @@ static uint32_t ssa_lanes(const std::vector<SsaNode> &nodes) {
 
 // `hoisted` receives declarations that belong before the step loop: the constants the body uses, and per round of products by
 // constants the ONE constant each lane needs (a lane-dependent, step-independent load instead of L loads and selects per step).
-static void ssa_emit(std::string &s, std::string &hoisted, std::vector<bool> &const_declared, const std::vector<SsaNode> &nodes, const JitGen &gen,
-                     const uint64_t *soff, const uint64_t *slen, const char *index, const char *sink, const char *tag) {
+static void ssa_emit(std::string &s, std::string &hoisted, std::vector<bool> &const_declared, const std::vector<SsaNode> &nodes, const AirProgram &p,
+                     const uint32_t L, const char *index, const char *sink, const char *tag) {
     char buf[256];
-    const uint32_t L = gen.lanes;
+    const uint64_t *soff = p.sd.offset, *slen = p.sd.len;
     int max_depth = 0;
     for (const SsaNode &n : nodes) max_depth = std::max(max_depth, n.depth);
     auto name = [&](int id) {
@@ -815,7 +789,7 @@ static void ssa_emit(std::string &s, std::string &hoisted, std::vector<bool> &co
                 if (!done[k] && nodes[pows[k]].kind == nodes[pows[first]].kind && nodes[pows[k]].aux == nodes[pows[first]].aux) { members.push_back(pows[k]); done[k] = true; }
             std::vector<uint32_t> e(GS_ELT / 4, 0u);
             if (nodes[pows[first]].kind == SsaNode::POWSHORT) e[0] = nodes[pows[first]].aux;
-            else memcpy(e.data(), gen.consts + (size_t)nodes[pows[first]].aux * GS_ELT, GS_ELT);
+            else memcpy(e.data(), p.consts + (size_t)nodes[pows[first]].aux * GS_ELT, GS_ELT);
             for (int id : members) s += "        fe " + name(id) + ";\n";
             s += "        {\n            fe x = " + name(nodes[members[0]].a) + ";\n";
             for (size_t i = 1; i < members.size(); i++) { snprintf(buf, sizeof buf, "            x = gs_pick(sub == %zuu, ", i); s += buf + name(nodes[members[i]].a) + ", x);\n"; }
@@ -1210,13 +1184,13 @@ static std::shared_ptr<const JitSource> jit_source_memo(const std::string &key, 
 
 // ---- trace segments --------------------------------------------------------------------------------------------------------------
 // returns GS_OK when the compiled kernel was launched, GS_ERR_UNSUPPORTED when the caller should interpret instead
-static bool jit_trace_source(std::string &s, JitGen &gen, const uint32_t *code, uint32_t ninstr, const uint32_t *icode, uint32_t init_ninstr,
-                             uint32_t vm_regs, uint32_t registers, const uint64_t *soff, const uint64_t *slen) {
+static bool jit_trace_source(std::string &s, JitGen &gen, const AirProgram &p, const AirProgram &init) {
     s = jit_preamble();
     char buf[256];
+    const uint32_t registers = p.registers, init_ninstr = init.ninstr;
     std::vector<SsaNode> main_nodes, init_nodes;
-    if (!ssa_build(main_nodes, gen, code, ninstr, vm_regs, true)) return false;
-    if (init_ninstr && !ssa_build(init_nodes, gen, icode, init_ninstr, vm_regs, false)) return false;
+    if (!ssa_build(main_nodes, gen, p, true)) return false;
+    if (init_ninstr && !ssa_build(init_nodes, gen, init, false)) return false;
     ssa_fuse_dots(main_nodes);
     ssa_fuse_dots(init_nodes);
     ssa_align_pows(main_nodes);
@@ -1237,10 +1211,10 @@ static bool jit_trace_source(std::string &s, JitGen &gen, const uint32_t *code, 
          "    const unsigned int gs_group = threadIdx.x & ~(GS_LANES - 1u);\n"
          "    const unsigned long long steps = segments * seglen;\n";
     for (uint32_t r = 0; r < registers; r++) { snprintf(buf, sizeof buf, "    fe r%u = first_rows[g * %uull + %uull], n%u;\n", r, registers, r, r); s += buf; }
-    std::vector<bool> const_declared(gen.nconsts, false);
+    std::vector<bool> const_declared(p.nconsts, false);
     std::string hoisted, init_body, main_body;
-    if (init_ninstr) ssa_emit(init_body, hoisted, const_declared, init_nodes, gen, soff, slen, "0ull", "n", "u");
-    ssa_emit(main_body, hoisted, const_declared, main_nodes, gen, soff, slen, "i", "n", "v");
+    if (init_ninstr) ssa_emit(init_body, hoisted, const_declared, init_nodes, init, gen.lanes, "0ull", "n", "u");
+    ssa_emit(main_body, hoisted, const_declared, main_nodes, p, gen.lanes, "i", "n", "v");
     s += hoisted;
     if (init_ninstr) {
         s += "    {\n";
@@ -1260,27 +1234,25 @@ static bool jit_trace_source(std::string &s, JitGen &gen, const uint32_t *code, 
     return true;
 }
 
-int gs_jit_trace_segments(gs_ctx *c, const uint32_t *code, uint32_t ninstr, const uint32_t *icode, uint32_t init_ninstr, const uint8_t *consts_host,
-                          uint32_t nconsts, uint32_t vm_regs, uint32_t registers, const uint64_t *soff, const uint64_t *slen, const uint8_t *statics_host,
-                          uint32_t nstatic, const fe *dconst, const fe *dstat, const fe *drows, uint64_t segments, uint64_t seglen, fe *out) {
-    JitGen gen;
-    gen.consts = consts_host;
-    gen.nconsts = nconsts;
-    gen.statics = statics_host;
-    gen.soff = soff;
-    gen.slen = slen;
-    gen.nstatic = nstatic;
-    std::string key("T");
-    key_add(key, code, (size_t)ninstr * 16);
-    key_add(key, icode, (size_t)init_ninstr * 16);
-    key_add(key, consts_host, (size_t)nconsts * GS_ELT);
-    key_add(key, soff, sizeof(uint64_t) * GS_AIR_MAX_REGISTERS);
-    key_add(key, slen, sizeof(uint64_t) * GS_AIR_MAX_REGISTERS);
-    const uint32_t shape[3] = {vm_regs, registers, nstatic};
+// everything of a program the generated source depends on (the init block shares all but its instructions)
+static std::string jit_key(const char *kind, const AirProgram &p, const AirProgram *init) {
+    std::string key(kind);
+    key_add(key, p.code, (size_t)p.ninstr * 16);
+    if (init) key_add(key, init->code, (size_t)init->ninstr * 16);
+    key_add(key, p.consts, (size_t)p.nconsts * GS_ELT);
+    key_add(key, &p.sd, sizeof p.sd);
+    const uint32_t shape[3] = {p.vm_regs, p.registers, p.nstatic};
     key_add(key, shape, sizeof shape);
-    for (uint32_t r = 0; r < nstatic; r++) key.push_back(gen.static_is_binary(r) ? '1' : '0');
+    return key;
+}
+
+int gs_jit_trace_segments(gs_ctx *c, const AirProgram &p, const AirProgram &init, const uint8_t *statics_host, const fe *dconst, const fe *dstat,
+                          const fe *drows, uint64_t segments, uint64_t seglen, fe *out) {
+    JitGen gen{1, statics_host};
+    std::string key = jit_key("T", p, &init);
+    for (uint32_t r = 0; r < p.nstatic; r++) key.push_back(gen.static_is_binary(p, r) ? '1' : '0');
     const std::shared_ptr<const JitSource> src = jit_source_memo(key, [&](JitSource &js) {
-        js.ok = jit_trace_source(js.source, gen, code, ninstr, icode, init_ninstr, vm_regs, registers, soff, slen);
+        js.ok = jit_trace_source(js.source, gen, p, init);
         js.lanes = gen.lanes;
     });
     if (!src->ok) return GS_ERR_UNSUPPORTED;
@@ -1293,7 +1265,7 @@ int gs_jit_trace_segments(gs_ctx *c, const uint32_t *code, uint32_t ninstr, cons
     constexpr unsigned block = 64;
     static_assert(block == 64, "gs_jit_trace: gs_swap[64], __launch_bounds__(64) and the lane groups assume one wave64 per block");
     const unsigned grid = (unsigned)((segments * gen.lanes + block - 1) / block);
-    gs_traffic(c, (uint64_t)registers * segments * (seglen + 1) * GS_ELT, (uint64_t)registers * segments * seglen, "gs_jit_trace");      // first rows in, the trace out
+    gs_traffic(c, (uint64_t)p.registers * segments * (seglen + 1) * GS_ELT, (uint64_t)p.registers * segments * seglen, "gs_jit_trace");      // first rows in, the trace out
     if (hipModuleLaunchKernel(k->fn, grid, 1, 1, block, 1, 1, 0, c->stream, args, nullptr) != hipSuccess) return GS_ERR_UNSUPPORTED;
     c->jit_launches++;
     return GS_OK;
@@ -1304,8 +1276,9 @@ int gs_jit_trace_segments(gs_ctx *c, const uint32_t *code, uint32_t ninstr, cons
 // point, no lanes.  A fused row is K x 25 v_mad into nine shared columns and ONE fold (gs_dot9: the constants are lane-uniform, their
 // limbs come out of scalar loads) instead of K products of 84 instructions and K - 1 additions: the 36 MDS products of a Poseidon
 // round are 6 x ~300 instructions instead of 36 x 84 + 30 x 12.
-static bool ssa_emit_flat(std::string &s, const std::vector<SsaNode> &nodes, const JitGen &gen, const uint64_t *soff, const uint64_t *slen) {
+static bool ssa_emit_flat(std::string &s, const std::vector<SsaNode> &nodes, const AirProgram &p) {
     char buf[256];
+    const uint64_t *soff = p.sd.offset, *slen = p.sd.len;
     auto name = [&](int id) {
         const SsaNode &n = nodes[id];
         char t[48];
@@ -1334,7 +1307,7 @@ static bool ssa_emit_flat(std::string &s, const std::vector<SsaNode> &nodes, con
             case SsaNode::POWSHORT: case SsaNode::POWLONG: {
                 std::vector<uint32_t> e(GS_ELT / 4, 0u);
                 if (n.kind == SsaNode::POWSHORT) e[0] = n.aux;
-                else memcpy(e.data(), gen.consts + (size_t)n.aux * GS_ELT, GS_ELT);
+                else memcpy(e.data(), p.consts + (size_t)n.aux * GS_ELT, GS_ELT);
                 s += "        fe " + name(id) + " = " + name(n.a) + ";\n        {\n";
                 emit_pow(s, name(id).c_str(), e);
                 s += "        }\n";
@@ -1356,47 +1329,46 @@ static bool ssa_emit_flat(std::string &s, const std::vector<SsaNode> &nodes, con
     return true;
 }
 
-static bool jit_constraints_source(std::string &s, const JitGen &gen, const uint32_t *code, uint32_t ninstr, uint32_t vm_regs, const uint64_t *soff,
-                                   const uint64_t *slen) {
+static bool jit_constraints_source(std::string &s, const AirProgram &p) {
     s = jit_preamble();
     char buf[256];
+    const uint32_t *const code = p.code, ninstr = p.ninstr;
     // register r at point j is p[r * prow + j * pstride]: the columns may be those of a larger domain read with a stride (the composition
     // domain inside the evaluation domain: gs_air_constraints_strided) — no plucked copy of the trace extension
     s += "extern \"C\" __global__ __launch_bounds__(128) void gs_jit_constraints(const fe *__restrict__ " GS_ARG(consts) ", const fe *__restrict__ " GS_ARG(p) ", unsigned long long nc,\n"
          "                                               unsigned long long shift, const fe *__restrict__ " GS_ARG(statics) ", fe *__restrict__ out,\n"
          "                                               unsigned long long prow, unsigned long long pstride) {\n"
          GS_WRAP3("consts", "p", "statics");
-    for (uint32_t t = 0; t < vm_regs; t++) { snprintf(buf, sizeof buf, "    fe t%u;\n", t); s += buf; }
+    for (uint32_t t = 0; t < p.vm_regs; t++) { snprintf(buf, sizeof buf, "    fe t%u;\n", t); s += buf; }
     s += "    for (unsigned long long j = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; j < nc; j += (unsigned long long)gridDim.x * blockDim.x) {\n"
          "        unsigned long long jn = j + shift;\n"
          "        if (jn >= nc) jn -= nc;\n"
          "        const unsigned long long jp = j * pstride, jnp = jn * pstride;\n";
     {   // linear layers present: the SSA route with fused rows (everything else: the register-by-register generator below)
         std::vector<SsaNode> nodes;
-        if (ssa_build(nodes, gen, code, ninstr, vm_regs, true, true)) {
+        if (ssa_build(nodes, JitGen(), p, true, true)) {
             ssa_fuse_dots(nodes);
             bool any = false;
             for (const SsaNode &n : nodes) any |= n.kind == SsaNode::DOT;
             std::string body;
-            if (any && ssa_emit_flat(body, nodes, gen, soff, slen)) {
+            if (any && ssa_emit_flat(body, nodes, p)) {
                 s += body + "    }\n}\n";
                 return true;
             }
         }
     }
     // loads of trace registers and outputs are memory operations here: rewrite them on the fly
-    std::vector<uint32_t> tmp(code, code + 4 * (size_t)ninstr);
     std::string body;
     for (uint32_t pc = 0; pc < ninstr; pc++) {
-        const uint32_t op = tmp[4 * pc], d = tmp[4 * pc + 1], a = tmp[4 * pc + 2];
-        if (op == J_LOADR) { snprintf(buf, sizeof buf, "        t%u = p[%uull * prow + jp];\n", d, a); body += buf; }
-        else if (op == J_LOADN) { snprintf(buf, sizeof buf, "        t%u = p[%uull * prow + jnp];\n", d, a); body += buf; }
-        else if (op == J_OUT) { snprintf(buf, sizeof buf, "        out[%uull * nc + j] = t%u;\n", d, a); body += buf; }
+        const uint32_t op = code[4 * pc], d = code[4 * pc + 1], a = code[4 * pc + 2];
+        if (op == OP_LOADR) { snprintf(buf, sizeof buf, "        t%u = p[%uull * prow + jp];\n", d, a); body += buf; }
+        else if (op == OP_LOADN) { snprintf(buf, sizeof buf, "        t%u = p[%uull * prow + jnp];\n", d, a); body += buf; }
+        else if (op == OP_OUT) { snprintf(buf, sizeof buf, "        out[%uull * nc + j] = t%u;\n", d, a); body += buf; }
         else {
             // runs of arithmetic go through the common generator (so that exponentiation groups are found)
             uint32_t end = pc;
-            while (end < ninstr && tmp[4 * end] != J_LOADR && tmp[4 * end] != J_LOADN && tmp[4 * end] != J_OUT) end++;
-            if (!jit_body(body, gen, tmp.data() + 4 * pc, end - pc, soff, slen, true, "r", nullptr, "j", "n")) return false;
+            while (end < ninstr && code[4 * end] != OP_LOADR && code[4 * end] != OP_LOADN && code[4 * end] != OP_OUT) end++;
+            if (!jit_body(body, p, code + 4 * pc, end - pc, true, "r", nullptr, "j", "n")) return false;
             pc = end - 1;
         }
     }
@@ -1405,31 +1377,20 @@ static bool jit_constraints_source(std::string &s, const JitGen &gen, const uint
     return true;
 }
 
-int gs_jit_constraints(gs_ctx *c, const uint32_t *code, uint32_t ninstr, const uint8_t *consts_host, uint32_t nconsts, uint32_t vm_regs,
-                       uint32_t registers, const uint64_t *soff, const uint64_t *slen, const fe *dconst, const fe *p, uint64_t nc, uint64_t shift,
-                       const fe *statics, fe *out, uint64_t prow, uint64_t pstride) {
-    JitGen gen;
-    gen.consts = consts_host;
-    gen.nconsts = nconsts;
-    std::string key("C");
-    key_add(key, code, (size_t)ninstr * 16);
-    key_add(key, consts_host, (size_t)nconsts * GS_ELT);
-    key_add(key, soff, sizeof(uint64_t) * GS_AIR_MAX_REGISTERS);
-    key_add(key, slen, sizeof(uint64_t) * GS_AIR_MAX_REGISTERS);
-    const uint32_t shape[2] = {vm_regs, registers};
-    key_add(key, shape, sizeof shape);
-    const std::shared_ptr<const JitSource> src = jit_source_memo(key, [&](JitSource &js) { js.ok = jit_constraints_source(js.source, gen, code, ninstr, vm_regs, soff, slen); });
+int gs_jit_constraints(gs_ctx *c, const AirProgram &p, const fe *dconst, const fe *columns, uint64_t nc, uint64_t shift, const fe *statics, fe *out,
+                       uint64_t prow, uint64_t pstride) {
+    const std::shared_ptr<const JitSource> src = jit_source_memo(jit_key("C", p, nullptr), [&](JitSource &js) { js.ok = jit_constraints_source(js.source, p); });
     if (!src->ok) return GS_ERR_UNSUPPORTED;
     const std::string &s = src->source;
     JitKernel *k = jit_get(c, s, "gs_jit_constraints");
     if (!k) return GS_ERR_UNSUPPORTED;
     unsigned long long a_nc = nc, a_shift = shift, a_prow = prow, a_pstride = pstride;
-    void *args[] = {(void *)&dconst, (void *)&p, (void *)&a_nc, (void *)&a_shift, (void *)&statics, (void *)&out, (void *)&a_prow, (void *)&a_pstride};
+    void *args[] = {(void *)&dconst, (void *)&columns, (void *)&a_nc, (void *)&a_shift, (void *)&statics, (void *)&out, (void *)&a_prow, (void *)&a_pstride};
     const unsigned block = 128, grid = gs_grid(nc, block, 256 * 16);
     {   // every register read at nc points (the neighbour row is the same vector), one vector per constraint written
         uint64_t outs = 0;
-        for (uint32_t pc = 0; pc < ninstr; pc++) outs += code[4 * pc] == J_OUT;
-        gs_traffic(c, nc * ((uint64_t)registers + outs) * GS_ELT, nc * outs, "gs_jit_constraints");
+        for (uint32_t pc = 0; pc < p.ninstr; pc++) outs += p.at(pc).op == OP_OUT;
+        gs_traffic(c, nc * ((uint64_t)p.registers + outs) * GS_ELT, nc * outs, "gs_jit_constraints");
     }
     if (hipModuleLaunchKernel(k->fn, grid, 1, 1, block, 1, 1, 0, c->stream, args, nullptr) != hipSuccess) return GS_ERR_UNSUPPORTED;
     c->jit_launches++;
@@ -1465,20 +1426,19 @@ extern "C" int gs_air_jit_check_statics(int kind, const uint32_t *code, uint32_t
                                         const uint8_t *consts_host, uint32_t nconsts, uint32_t vm_regs, uint32_t registers, const uint64_t *static_lens,
                                         uint32_t nstatic, const uint8_t *static_values_host, char *log_out, uint64_t log_cap) {
     if (!code || !ninstr || nstatic > GS_AIR_MAX_REGISTERS || (nstatic && !static_lens) || (nconsts && !consts_host)) return GS_ERR_ARG;
-    JitGen gen;
-    gen.consts = consts_host;
-    gen.nconsts = nconsts;
-    uint64_t soff[GS_AIR_MAX_REGISTERS], slen[GS_AIR_MAX_REGISTERS], off = 0;
-    for (uint32_t s = 0; s < GS_AIR_MAX_REGISTERS; s++) {
-        soff[s] = off;
-        slen[s] = s < nstatic ? static_lens[s] : 1;
-        if (s < nstatic) off += static_lens[s];
+    // (an evaluator's number of constraints is no argument of this hook: its OUT destinations are not bounded here)
+    AirProgram p {code, ninstr, consts_host, nconsts, vm_regs, registers, nstatic, kind == 0 ? registers : UINT32_MAX};
+    if (!air_static_layout(static_lens, nstatic, p.sd)) return GS_ERR_ARG;
+    const AirProgram init = p.with_code(init_code, kind == 0 ? init_ninstr : 0);
+    char msg[96];
+    if (!air_validate(p, kind != 0, true, msg, sizeof msg) || (init.ninstr && !air_validate(init, false, false, msg, sizeof msg))) {
+        if (log_out && log_cap) snprintf(log_out, log_cap, "%s", msg);
+        return GS_ERR_UNSUPPORTED;
     }
-    if (kind == 0 && static_values_host) { gen.statics = static_values_host; gen.soff = soff; gen.slen = slen; gen.nstatic = nstatic; }
+    JitGen gen{1, kind == 0 ? static_values_host : nullptr};
     std::string src, log;
     const auto t0 = std::chrono::steady_clock::now();
-    const bool ok = kind == 0 ? jit_trace_source(src, gen, code, ninstr, init_code, init_ninstr, vm_regs, registers, soff, slen)
-                              : jit_constraints_source(src, gen, code, ninstr, vm_regs, soff, slen);
+    const bool ok = kind == 0 ? jit_trace_source(src, gen, p, init) : jit_constraints_source(src, p);
     if (getenv("GSTARK_AIR_JIT_VERBOSE"))
         fprintf(stderr, "[gstark] source of the %s program generated in %.1f us (%zu bytes)\n", kind == 0 ? "trace" : "constraint",
                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), src.size());

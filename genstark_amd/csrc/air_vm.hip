@@ -11,14 +11,7 @@
 #endif
 #include "host_field.h"
 #include "host_pow.h"
-
-enum { OP_LOADC = 0, OP_LOADR = 1, OP_LOADN = 2, OP_LOADS = 3, OP_ADDV = 4, OP_SUBV = 5, OP_MULV = 6, OP_POW = 7, OP_POWC = 8, OP_OUT = 9 };
-
-
-struct StaticDesc {
-    uint64_t offset[GS_AIR_MAX_REGISTERS];  // element offset into the concatenated table
-    uint64_t len[GS_AIR_MAX_REGISTERS];
-};
+#include "air_program.h"
 
 template <int NREG>
 __global__ void k_air_constraints(const uint4 *__restrict__ code, uint32_t ninstr, const fe *__restrict__ consts,
@@ -278,27 +271,34 @@ __global__ void k_air_trace_segments(const uint4 *__restrict__ code, uint32_t ni
 #undef row
 #undef next
 
-static int check_program(gs_ctx *c, const uint32_t *code, uint32_t ninstr, uint32_t nconsts, uint32_t vm_regs, uint32_t registers,
-                         uint32_t nstatic, uint32_t nout, bool allow_next) {
-    if (!code || !ninstr) return gs_fail(c, GS_ERR_ARG, "air program: empty");
-    if (vm_regs == 0 || vm_regs > GS_AIR_MAX_VM_REGS) return gs_fail(c, GS_ERR_ARG, "air program: vm_regs must be in 1..%d", GS_AIR_MAX_VM_REGS);
-    if (registers == 0 || registers > GS_AIR_MAX_REGISTERS || nstatic > GS_AIR_MAX_REGISTERS) return gs_fail(c, GS_ERR_ARG, "air program: too many registers");
-    for (uint32_t pc = 0; pc < ninstr; pc++) {
-        const uint32_t op = code[4 * pc], dst = code[4 * pc + 1], a = code[4 * pc + 2], b = code[4 * pc + 3];
-        bool ok = true;
-        switch (op) {
-            case OP_LOADC: ok = dst < vm_regs && a < nconsts; break;
-            case OP_LOADR: ok = dst < vm_regs && a < registers; break;
-            case OP_LOADN: ok = allow_next && dst < vm_regs && a < registers; break;
-            case OP_LOADS: ok = dst < vm_regs && a < nstatic; break;
-            case OP_ADDV: case OP_SUBV: case OP_MULV: ok = dst < vm_regs && a < vm_regs && b < vm_regs; break;
-            case OP_POW: ok = dst < vm_regs && a < vm_regs; break;
-            case OP_POWC: ok = dst < vm_regs && a < vm_regs && b < nconsts; break;
-            case OP_OUT: ok = dst < nout && a < vm_regs; break;
-            default: ok = false;
-        }
-        if (!ok) return gs_fail(c, GS_ERR_ARG, "air program: invalid instruction %u (op %u)", pc, op);
+// the program of an entry point as one value: validated (nout: what OUT may name) and with its static layout
+template <class Len>
+static int checked_program(gs_ctx *c, AirProgram &p, bool allow_next, const Len *static_lens, uint64_t *nstat = nullptr) {
+    char msg[96];
+    if (!air_validate(p, allow_next, true, msg, sizeof msg)) return gs_fail(c, GS_ERR_ARG, "%s", msg);
+    if (!air_static_layout(static_lens, p.nstatic, p.sd, nstat)) return gs_fail(c, GS_ERR_ARG, "air program: empty static table");
+    return GS_OK;
+}
+
+// Host parts -> ONE device block, part k at at[k] (256-byte aligned): assembled in the upload ring and sent with one asynchronous copy
+// (no round trip; the caller's buffers are free at once), or part by part when they do not fit the ring (a very long list of first rows)
+struct HostPart { const void *src; uint64_t bytes; };
+template <int N>
+static int stage_parts(gs_ctx *c, const HostPart (&parts)[N], uint8_t *(&at)[N], void **block) {
+    uint64_t off[N], total = 0;
+    for (int k = 0; k < N; k++) { off[k] = total; total += (parts[k].bytes + 255) & ~(uint64_t)255; }
+    int rc = gs_tmp_alloc(c, total, block);
+    if (rc) return rc;
+    void *h = nullptr;
+    if ((rc = gs_push_reserve(c, total, &h)) == GS_OK) {
+        for (int k = 0; k < N; k++) if (parts[k].bytes) memcpy((uint8_t *)h + off[k], parts[k].src, (size_t)parts[k].bytes);
+        rc = gs_push_commit(c, *block, h, total);
+    } else if (rc == GS_ERR_UNSUPPORTED) {
+        rc = GS_OK;
+        for (int k = 0; k < N && rc == GS_OK; k++) rc = parts[k].bytes ? gs_push(c, (uint8_t *)*block + off[k], parts[k].src, parts[k].bytes) : GS_OK;
     }
+    if (rc) { gs_tmp_free(c, *block); return rc; }
+    for (int k = 0; k < N; k++) at[k] = (uint8_t *)*block + off[k];
     return GS_OK;
 }
 
@@ -349,7 +349,6 @@ static int host_trace(gs_ctx *c, const uint32_t *code_host, uint32_t ninstr, con
     {
         const uint8_t *p = static_values_host;
         for (uint32_t s = 0; s < nstatic; s++) {
-            if (!static_periods_host[s]) return gs_fail(c, GS_ERR_ARG, "air_trace: empty static register");
             statics[s].resize(static_periods_host[s]);
             for (uint32_t i = 0; i < static_periods_host[s]; i++, p += GS_ELT) statics[s][i] = hf_load(p);
         }
@@ -391,52 +390,31 @@ int gs_air_constraints_strided(gs_ctx *c, const uint32_t *code_host, uint32_t ni
                                uint32_t registers, uint32_t constraints, const void *p_comp, uint64_t prow, uint64_t pstride, uint64_t nc, uint64_t shift,
                                const void *static_tables, const uint64_t *static_lens_host, uint32_t nstatic, void *out) {
     if (!c || !p_comp || !out || (!consts_host && nconsts) || (nstatic && (!static_tables || !static_lens_host))) return GS_ERR_ARG;
-    int rc = check_program(c, code_host, ninstr, nconsts, vm_regs, registers, nstatic, constraints, true);
+    AirProgram prog {code_host, ninstr, consts_host, nconsts, vm_regs, registers, nstatic, constraints};
+    int rc = checked_program(c, prog, true, static_lens_host);
     if (rc) return rc;
     if (!nc) return gs_fail(c, GS_ERR_ARG, "air_constraints: empty domain");
     if (!pstride || (nc - 1) > (UINT64_MAX / pstride) || (nc - 1) * pstride >= prow)
         return gs_fail(c, GS_ERR_ARG, "air_constraints: %llu points at stride %llu do not fit rows of %llu elements", (unsigned long long)nc,
                        (unsigned long long)pstride, (unsigned long long)prow);
-    StaticDesc sd;
-    uint64_t off = 0;
-    for (uint32_t s = 0; s < GS_AIR_MAX_REGISTERS; s++) {
-        sd.offset[s] = off;
-        sd.len[s] = s < nstatic ? static_lens_host[s] : 1;
-        if (s < nstatic) {
-            if (!static_lens_host[s]) return gs_fail(c, GS_ERR_ARG, "air_constraints: empty static table");
-            off += static_lens_host[s];
-        }
-    }
-    // program + constants to device scratch (small; one sync so the staging buffer can be reused)
-    const uint64_t code_bytes = ((uint64_t)ninstr * 16 + 255) & ~(uint64_t)255, const_bytes = (uint64_t)(nconsts ? nconsts : 1) * GS_ELT;
+    // program + constants to device scratch
+    const HostPart parts[2] = {{code_host, (uint64_t)ninstr * 16}, {consts_host, (uint64_t)nconsts * GS_ELT}};
+    uint8_t *at[2];
     void *dprog;
-    if ((rc = gs_tmp_alloc(c, code_bytes + const_bytes, &dprog))) return rc;
-    {   // assembled in the upload ring, one asynchronous copy (no round trip; the caller's buffers are free at once)
-        void *h = nullptr;
-        if ((rc = gs_push_reserve(c, code_bytes + const_bytes, &h)) == GS_OK) {
-            memcpy(h, code_host, (size_t)ninstr * 16);
-            if (nconsts) memcpy((uint8_t *)h + code_bytes, consts_host, (size_t)nconsts * GS_ELT);
-            rc = gs_push_commit(c, dprog, h, code_bytes + const_bytes);
-        } else if (rc == GS_ERR_UNSUPPORTED) {
-            rc = gs_push(c, dprog, code_host, (uint64_t)ninstr * 16);
-            if (rc == GS_OK && nconsts) rc = gs_push(c, (uint8_t *)dprog + code_bytes, consts_host, (uint64_t)nconsts * GS_ELT);
-        }
-        if (rc) { gs_tmp_free(c, dprog); return rc; }
-    }
+    if ((rc = stage_parts(c, parts, at, &dprog))) return rc;
+    const uint4 *dcode = (const uint4 *)at[0];
+    const fe *dconst = (const fe *)at[1];
     if (c->air_jit) {   // compiled form of the program (air_jit.hip); the interpreter below is the fallback
-        int jrc = gs_jit_constraints(c, code_host, ninstr, consts_host, nconsts, vm_regs, registers, sd.offset, sd.len, (const fe *)((uint8_t *)dprog + code_bytes),
-                                     (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, (fe *)out, prow, pstride);
+        int jrc = gs_jit_constraints(c, prog, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, (fe *)out, prow, pstride);
         if (jrc == GS_OK) { gs_tmp_free(c, dprog); return GS_OK; }
     }
-    const uint4 *dcode = (const uint4 *)dprog;
-    const fe *dconst = (const fe *)((uint8_t *)dprog + code_bytes);
     dim3 grid(gs_grid(nc)), block(256);
     if (vm_regs <= 16)
-        hipLaunchKernelGGL(k_air_constraints<16>, grid, block, 0, c->stream, dcode, ninstr, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, sd, (fe *)out, prow, pstride);
+        hipLaunchKernelGGL(k_air_constraints<16>, grid, block, 0, c->stream, dcode, ninstr, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, prog.sd, (fe *)out, prow, pstride);
     else if (vm_regs <= 32)
-        hipLaunchKernelGGL(k_air_constraints<32>, grid, block, 0, c->stream, dcode, ninstr, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, sd, (fe *)out, prow, pstride);
+        hipLaunchKernelGGL(k_air_constraints<32>, grid, block, 0, c->stream, dcode, ninstr, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, prog.sd, (fe *)out, prow, pstride);
     else
-        hipLaunchKernelGGL(k_air_constraints<64>, grid, block, 0, c->stream, dcode, ninstr, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, sd, (fe *)out, prow, pstride);
+        hipLaunchKernelGGL(k_air_constraints<64>, grid, block, 0, c->stream, dcode, ninstr, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, prog.sd, (fe *)out, prow, pstride);
     hipError_t e = hipGetLastError();
     gs_tmp_free(c, dprog);  // stream-ordered reuse: later users of the block are queued behind this kernel
     if (e != hipSuccess) return gs_fail(c, GS_ERR_DEVICE, "air_constraints launch: %s", hipGetErrorString(e));
@@ -448,70 +426,42 @@ int gs_air_trace_segments(gs_ctx *c, const uint32_t *code_host, uint32_t ninstr,
                           const uint32_t *static_periods_host, uint32_t nstatic, const uint8_t *first_rows_host, uint64_t segments,
                           uint64_t segment_len, void *out) {
     if (!c || !first_rows_host || !out || (!consts_host && nconsts) || (nstatic && (!static_values_host || !static_periods_host))) return GS_ERR_ARG;
-    int rc = check_program(c, code_host, ninstr, nconsts, vm_regs, registers, nstatic, registers, false);
-    if (rc) return rc;
-    if (init_ninstr && (rc = check_program(c, init_code_host, init_ninstr, nconsts, vm_regs, registers, 0, registers, false))) return rc;
-    if (!segments || !segment_len) return gs_fail(c, GS_ERR_ARG, "air_trace_segments: empty");
-    StaticDesc sd;
+    AirProgram prog {code_host, ninstr, consts_host, nconsts, vm_regs, registers, nstatic, registers};
     uint64_t nstat = 0;
-    for (uint32_t s = 0; s < GS_AIR_MAX_REGISTERS; s++) {
-        sd.offset[s] = nstat;
-        sd.len[s] = s < nstatic ? static_periods_host[s] : 1;
-        if (s < nstatic) {
-            if (!static_periods_host[s]) return gs_fail(c, GS_ERR_ARG, "air_trace_segments: empty static register");
-            nstat += static_periods_host[s];
-        }
-    }
+    int rc = checked_program(c, prog, false, static_periods_host, &nstat);
+    if (rc) return rc;
+    const AirProgram init = prog.with_code(init_code_host, init_ninstr);
+    char msg[96];
+    if (init_ninstr && !air_validate(init, false, false, msg, sizeof msg)) return gs_fail(c, GS_ERR_ARG, "%s", msg);
+    if (!segments || !segment_len) return gs_fail(c, GS_ERR_ARG, "air_trace_segments: empty");
     if (segments <= c->host_trace_segments)
         return host_trace(c, code_host, ninstr, init_code_host, init_ninstr, consts_host, nconsts, vm_regs, registers, static_values_host,
                           static_periods_host, nstatic, first_rows_host, segments, segment_len, out);
-    // program, constants, static values and first rows -> one device block (pageable caller memory: one sync)
-    const uint64_t main_b = ((uint64_t)ninstr * 16 + 255) & ~(uint64_t)255, code_b = main_b + (((uint64_t)init_ninstr * 16 + 255) & ~(uint64_t)255);
-    const uint64_t const_b = ((uint64_t)(nconsts ? nconsts : 1) * GS_ELT + 255) & ~(uint64_t)255;
-    const uint64_t stat_b = ((nstat ? nstat : 1) * GS_ELT + 255) & ~(uint64_t)255, rows_b = segments * registers * GS_ELT;
+    // program, constants, static values and first rows -> one device block
+    const HostPart parts[5] = {{code_host, (uint64_t)ninstr * 16}, {init_code_host, (uint64_t)init_ninstr * 16}, {consts_host, (uint64_t)nconsts * GS_ELT},
+                               {static_values_host, nstat * GS_ELT}, {first_rows_host, segments * registers * GS_ELT}};
+    uint8_t *at[5];
     void *d;
-    if ((rc = gs_tmp_alloc(c, code_b + const_b + stat_b + rows_b, &d))) return rc;
-    uint8_t *p = (uint8_t *)d;
-    {   // assembled in the upload ring, one asynchronous copy (no round trip; the caller's buffers are free at once)
-        void *h = nullptr;
-        const uint64_t total = code_b + const_b + stat_b + rows_b;
-        if ((rc = gs_push_reserve(c, total, &h)) == GS_OK) {
-            uint8_t *hp = (uint8_t *)h;
-            memcpy(hp, code_host, (size_t)ninstr * 16);
-            if (init_ninstr) memcpy(hp + main_b, init_code_host, (size_t)init_ninstr * 16);
-            if (nconsts) memcpy(hp + code_b, consts_host, (size_t)nconsts * GS_ELT);
-            if (nstat) memcpy(hp + code_b + const_b, static_values_host, (size_t)nstat * GS_ELT);
-            memcpy(hp + code_b + const_b + stat_b, first_rows_host, (size_t)rows_b);
-            rc = gs_push_commit(c, p, h, total);
-        } else if (rc == GS_ERR_UNSUPPORTED) {      // a very long list of first rows: part by part
-            rc = gs_push(c, p, code_host, (uint64_t)ninstr * 16);
-            if (rc == GS_OK && init_ninstr) rc = gs_push(c, p + main_b, init_code_host, (uint64_t)init_ninstr * 16);
-            if (rc == GS_OK && nconsts) rc = gs_push(c, p + code_b, consts_host, (uint64_t)nconsts * GS_ELT);
-            if (rc == GS_OK && nstat) rc = gs_push(c, p + code_b + const_b, static_values_host, nstat * GS_ELT);
-            if (rc == GS_OK) rc = gs_push(c, p + code_b + const_b + stat_b, first_rows_host, rows_b);
-        }
-        if (rc) { gs_tmp_free(c, d); return rc; }
-    }
-    const uint4 *dcode = (const uint4 *)p, *dinit = (const uint4 *)(p + main_b);
-    const fe *dconst = (const fe *)(p + code_b), *dstat = (const fe *)(p + code_b + const_b), *drows = (const fe *)(p + code_b + const_b + stat_b);
+    if ((rc = stage_parts(c, parts, at, &d))) return rc;
+    const uint4 *dcode = (const uint4 *)at[0], *dinit = (const uint4 *)at[1];
+    const fe *dconst = (const fe *)at[2], *dstat = (const fe *)at[3], *drows = (const fe *)at[4];
     if (c->air_jit) {   // compiled form of the program (air_jit.hip); the interpreter below is the fallback
-        int jrc = gs_jit_trace_segments(c, code_host, ninstr, init_code_host, init_ninstr, consts_host, nconsts, vm_regs, registers, sd.offset, sd.len, nstat ? static_values_host : nullptr, nstatic, dconst, dstat, drows,
-                                        segments, segment_len, (fe *)out);
+        int jrc = gs_jit_trace_segments(c, prog, init, nstat ? static_values_host : nullptr, dconst, dstat, drows, segments, segment_len, (fe *)out);
         if (jrc == GS_OK) { gs_tmp_free(c, d); return GS_OK; }
     }
-    // 4 lanes per segment when the program has a layer of long exponentiations to split (same rule as the code generator's)
+    // 4 lanes per segment when the program has a layer of long exponentiations to split: a POWC with an exponent beyond a word heads a group
     uint32_t lanes = 1;
-    for (uint32_t pc = 0; pc + 1 < ninstr && lanes == 1; pc++) {
-        const uint32_t *in = code_host + 4 * pc, *nx = in + 4;
-        if (in[0] != OP_POWC || nx[0] != OP_POWC || nx[3] != in[3] || nx[2] == in[1]) continue;
-        const uint8_t *ex = consts_host + (size_t)in[3] * GS_ELT;
+    for (uint32_t pc = 0; pc < ninstr && lanes == 1; pc++) {
+        const AirIns in = prog.at(pc);
+        if (in.op != OP_POWC || air_pow_group(code_host, ninstr, pc) < 2) continue;
+        const uint8_t *ex = consts_host + (size_t)in.b * GS_ELT;
         for (int i = 4; i < GS_ELT; i++)
             if (ex[i]) lanes = 4;
     }
     dim3 block(64), grid((unsigned)((segments * lanes + 63) / 64));   // one wave per 64 / lanes segments: the few long-running threads spread over the CUs
     const uint64_t lds_bytes = ((uint64_t)vm_regs + 2ull * registers) * 64 * GS_ELT;
 #define GS_LAUNCH_TRACE(N, L, SH)                                                                                                        \
-    hipLaunchKernelGGL((k_air_trace_segments<N, L>), grid, block, SH, c->stream, dcode, ninstr, dinit, init_ninstr, dconst, dstat, sd, drows, \
+    hipLaunchKernelGGL((k_air_trace_segments<N, L>), grid, block, SH, c->stream, dcode, ninstr, dinit, init_ninstr, dconst, dstat, prog.sd, drows, \
                        registers, segments, segment_len, vm_regs, lanes, (fe *)out)
     if (lds_bytes <= 160 * 1024) {   // gfx950: 160 KB of LDS per workgroup
         static bool attr_set = false;
@@ -535,8 +485,8 @@ int gs_air_trace(gs_ctx *c, const uint32_t *code_host, uint32_t ninstr, const ui
                  uint32_t registers, const uint8_t *static_values_host, const uint32_t *static_periods_host, uint32_t nstatic,
                  const uint8_t *first_row_host, uint64_t steps, void *out) {
     if (!c || !first_row_host || !out || (!consts_host && nconsts) || (nstatic && (!static_values_host || !static_periods_host))) return GS_ERR_ARG;
-    int rc = check_program(c, code_host, ninstr, nconsts, vm_regs, registers, nstatic, registers, false);
-    if (rc) return rc;
+    AirProgram prog {code_host, ninstr, consts_host, nconsts, vm_regs, registers, nstatic, registers};
+    if (int rc = checked_program(c, prog, false, static_periods_host)) return rc;
     if (!steps) return gs_fail(c, GS_ERR_ARG, "air_trace: empty");
     return host_trace(c, code_host, ninstr, nullptr, 0, consts_host, nconsts, vm_regs, registers, static_values_host, static_periods_host, nstatic,
                       first_row_host, 1, steps, out);

@@ -34,6 +34,7 @@
 #include "gf_wide.h"
 #endif
 #include "host_field.h"
+#include "air_program.h"      // opcodes and validator of AIR programs (verifier.h)
 #include "host_poly.h"
 #include "host_hash.h"
 

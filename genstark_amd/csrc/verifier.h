@@ -121,27 +121,24 @@ bool merkle_check(int alg, const Bytes &root, const std::vector<uint64_t> &index
     return merkle_verify_batch(alg, root.data(), indexes, digests, mp.nodes, mp.depth);
 }
 
-// the constraint evaluator of an AIR given as a register-machine program (kind 1), on host scalars: genstark_amd/air_generic.py
-// Program.run (what the device runs in k_air_constraints).  Opcodes as in include/gstark.h.
-std::vector<F> run_program(const gs_prover_air &air, const std::vector<F> &cur, const std::vector<F> &nxt, const std::vector<F> &statics) {
-    enum { LOADC, LOADR, LOADN, LOADS, ADD, SUB, MUL, POW, POWC, OUT };
-    std::vector<F> vm(air.vm_regs ? air.vm_regs : 1, (F)0), out(air.nconstraints, (F)0);
-    auto konst = [&](uint32_t i) { if (i >= air.nconsts) fail(GS_ERR_ARG, "program: constant index out of range"); return load_elem(air.consts + ELEM * i); };
-    auto r = [&](uint32_t i) -> F & { if (i >= vm.size()) fail(GS_ERR_ARG, "program: register out of range"); return vm[i]; };
-    for (uint32_t k = 0; k < air.e_ninstr; k++) {
-        const uint32_t op = air.e_code[4 * k], d = air.e_code[4 * k + 1], a = air.e_code[4 * k + 2], b = air.e_code[4 * k + 3];
-        switch (op) {
-            case LOADC: r(d) = konst(a); break;
-            case LOADR: if (a >= cur.size()) fail(GS_ERR_ARG, "program: trace register out of range"); r(d) = cur[a]; break;
-            case LOADN: if (a >= nxt.size()) fail(GS_ERR_ARG, "program: trace register out of range"); r(d) = nxt[a]; break;
-            case LOADS: if (a >= statics.size()) fail(GS_ERR_ARG, "program: static register out of range"); r(d) = statics[a]; break;
-            case ADD: r(d) = hf_add(r(a), r(b)); break;
-            case SUB: r(d) = hf_sub(r(a), r(b)); break;
-            case MUL: r(d) = hf_mul(r(a), r(b)); break;
-            case POW: r(d) = hf_pow(r(a), (hfe)(uint64_t)b); break;
-            case POWC: r(d) = hf_pow(r(a), konst(b)); break;
-            case OUT: if (d >= out.size()) fail(GS_ERR_ARG, "program: output out of range"); out[d] = r(a); break;
-            default: fail(GS_ERR_ARG, "program: unknown opcode %u", op);
+// the constraint evaluator of an AIR given as a register-machine program (kind 1), on host scalars (what the device runs in
+// k_air_constraints).  verify_impl validates it ONCE per job (air_program.h): every index used here lies inside cur / nxt (registers),
+// statics (nstatic), the constants, the scratch file and the outputs (nconstraints).
+std::vector<F> run_program(const AirProgram &p, const std::vector<F> &cur, const std::vector<F> &nxt, const std::vector<F> &statics) {
+    std::vector<F> vm(p.vm_regs, (F)0), out(p.nout, (F)0);
+    for (uint32_t k = 0; k < p.ninstr; k++) {
+        const AirIns i = p.at(k);
+        switch (i.op) {
+            case OP_LOADC: vm[i.dst] = load_elem(p.consts + ELEM * i.a); break;
+            case OP_LOADR: vm[i.dst] = cur[i.a]; break;
+            case OP_LOADN: vm[i.dst] = nxt[i.a]; break;
+            case OP_LOADS: vm[i.dst] = statics[i.a]; break;
+            case OP_ADDV: vm[i.dst] = hf_add(vm[i.a], vm[i.b]); break;
+            case OP_SUBV: vm[i.dst] = hf_sub(vm[i.a], vm[i.b]); break;
+            case OP_MULV: vm[i.dst] = hf_mul(vm[i.a], vm[i.b]); break;
+            case OP_POW: vm[i.dst] = hf_pow(vm[i.a], (hfe)(uint64_t)i.b); break;
+            case OP_POWC: vm[i.dst] = hf_pow(vm[i.a], load_elem(p.consts + ELEM * i.b)); break;
+            default: out[i.dst] = vm[i.a]; break;      // OP_OUT (the validator admits no other opcode)
         }
     }
     return out;
@@ -377,6 +374,9 @@ void device_values(const DeviceVerify &dev, const Plan &plan, const std::vector<
 // dev = null: everything on this host core (gs_prover_verify)
 void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_len, const DeviceVerify *dev) {
     const gs_prover_air &air = job.air;
+    const AirProgram evaluator{air.e_code, air.e_ninstr, air.consts, air.nconsts, air.vm_regs, air.registers, air.nstatic, air.nconstraints};
+    char emsg[96] = "air program: its constants are missing";
+    if (air.kind == 1 && ((air.nconsts && !air.consts) || !air_validate(evaluator, true, true, emsg, sizeof emsg))) fail(GS_ERR_ARG, "%s", emsg);
     const uint64_t E = job.extension_factor;
     const uint32_t R = air.registers, S = air.nsecret;
     const int alg = job.hash_alg;
@@ -548,7 +548,7 @@ void verify_impl(const gs_prover_job &job, const uint8_t *proof, uint64_t proof_
             return std::vector<F>{hf_sub(n[0], hf_add(x3, statics[0]))};
         }
         for (F v : s) statics.push_back(v);
-        return run_program(air, p, n, statics);
+        return run_program(evaluator, p, n, statics);
     };
 
     // ----- spot-check positions and the evaluation tree (lib/Stark.ts:183-216)

@@ -1,7 +1,9 @@
 """AIR programs for the register machine of include/gstark.h, with a model of that machine on Python integers.
 
-The machine has four implementations (the code generator of csrc/air_jit.hip, the device interpreter of csrc/air_vm.hip, its host_run
-and the oracle's loop), each with optimisations of its own.  This module holds what tests/test_air_programs.py compares them with and on:
+The machine has four native implementations, each with optimisations of its own (the code generator of csrc/air_jit.hip, the device
+interpreters of csrc/air_vm.hip, its host_run and the verifier's run_program) beside the oracle's loop; what they must agree on before
+they run — opcodes, validator, static layout, grouping rule — is stated once in csrc/air_program.h.  This module holds what
+tests/test_air_programs.py and tests/test_air_program_header.py compare them with and on:
   - run_trace / run_constraints: the machine written straight from the header's comment (about forty lines);
   - one builder per branch of the generator and the interpreters (targeted_programs, constraint_programs);
   - a seeded generator of programs at instruction level (generated_program);

@@ -10,7 +10,7 @@ out=${1:-/tmp/gstark_sanitized_$(id -u)}
 mkdir -p "$out"
 SAN="-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
 cd "$root/genstark_amd/csrc"
-deps="prover.cc prover_dist.h verifier.h host_hash.h host_poly.h host_field.h host_field_small.h host_field_wide.h gf_wide.h ../../include/gstark.h ../../include/gstark_comm.h ../../include/gstark_prover.h ../../include/gstark_boundary.h $root/tools/build_sanitized.sh"
+deps="prover.cc prover_dist.h verifier.h air_program.h host_hash.h host_poly.h host_field.h host_field_small.h host_field_wide.h gf_wide.h ../../include/gstark.h ../../include/gstark_comm.h ../../include/gstark_prover.h ../../include/gstark_boundary.h $root/tools/build_sanitized.sh"
 build() {   # <output> <extra flags>
   local stale=0 d
   for d in $deps; do [ $d -nt "$out/$1" ] && stale=1; done
