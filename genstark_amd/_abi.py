@@ -195,6 +195,13 @@ _CURVE_SIGNATURES = {
 }
 CURVE_SYMBOLS = tuple(_CURVE_SIGNATURES)
 
+# include/gstark_diagnose.h: the scan of the statement diagnosis; optional in the same way (a driver bound to a library without it
+# downloads the matrix and scans it on the host)
+_DIAGNOSE_SIGNATURES = {
+    'gs_nonzero_spans': (_int, [_vp, _vp, _u64, _u64, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+}
+DIAGNOSE_SYMBOLS = tuple(_DIAGNOSE_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -211,7 +218,7 @@ def load_library(path):
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
                               + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
-                              + list(_CURVE_SIGNATURES.items())):
+                              + list(_CURVE_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -27,6 +27,7 @@
 #include "../../include/gstark_comm.h"
 #include "../../include/gstark_boundary.h"
 #include "../../include/gstark_mimc.h"
+#include "../../include/gstark_diagnose.h"
 // One build of this file per field flavour of the ABI library (csrc/build.sh: the same -DGS_SMALL_Q / -DGS_WIDE_BITS): the host-side
 // scalars (domain roots, Fiat-Shamir coefficients, boundary interpolants, the remainder check) use the flavour's host arithmetic,
 // elements are gs_element_size() bytes on the ABI and in the proof.
@@ -49,9 +50,9 @@ namespace {
     X(gs_small_eval_poly) X(gs_pseudorandom_indexes) X(gs_mimc_trace) X(gs_mimc_constraints) X(gs_air_trace)                    \
     X(gs_air_trace_segments) X(gs_air_constraints) X(gs_air_constraints_strided) X(gs_composition_tail) X(gs_composition_tail_coset) X(gs_zero_poly_inverses) X(gs_div_by_domain_roots) X(gs_mimc_composition) X(gs_fri_fold) X(gs_fri_fold_seeded) X(gs_defer_begin) X(gs_defer_end) X(gs_readback_post) X(gs_readback_wait) X(gs_merkle_commit_rows_seed) X(gs_fri_fold_at) \
     X(gs_vec_mul_scalar) X(gs_copy) X(gs_gather_words) X(gs_transpose_records) X(gs_fri_fold_seeded_scaled) X(gs_fri_layers) X(gs_sync) X(gs_zero_poly_inverses_coset) X(gs_div_by_domain_roots_coset)
-// ... and the entry points an implementation may lack (include/gstark_boundary.h): null then, and the driver keeps its host path
+// ... and the entry points an implementation may lack (include/gstark_boundary.h, gstark_diagnose.h): null then, and the driver keeps its host path
 // (include/gstark_mimc.h: without them the fused MiMC branch calls gs_mimc_composition)
-#define GS_API_OPTIONAL_LIST(X) X(gs_boundary_polys) X(gs_eval_polys_at_points) X(gs_mimc_composition_prepare) X(gs_mimc_composition_tables)
+#define GS_API_OPTIONAL_LIST(X) X(gs_boundary_polys) X(gs_eval_polys_at_points) X(gs_mimc_composition_prepare) X(gs_mimc_composition_tables) X(gs_nonzero_spans)
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
     GS_API_LIST(X)
@@ -1378,3 +1379,6 @@ static void prove_impl(Ctx &x, const gs_prover_job &job, Bytes &out) {
 
 // ---- Stark.verify(): the CPU-side half of the acceptance loop, native
 #include "verifier.h"
+
+// ---- why a statement does not prove: the same job, no proof (include/gstark_diagnose.h)
+#include "diagnose.h"

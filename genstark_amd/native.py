@@ -63,6 +63,16 @@ class _Stats(C.Structure):
                 ('nreadme', C.c_uint32), ('readme_ms', C.c_double * 16), ('readme_label', (C.c_char * 160) * 16)]
 
 
+class _DiagnoseConstraint(C.Structure):     # struct gs_diagnose_constraint (include/gstark_diagnose.h)
+    _fields_ = [('violations', C.c_uint64), ('first_step', C.c_uint64), ('last_step', C.c_uint64), ('first_value', C.c_uint8 * ELT_MAX),
+                ('degree', C.c_uint64), ('limit', C.c_uint64), ('declared', C.c_uint32), ('needed', C.c_uint32), ('at_least', C.c_uint32),
+                ('all_zero', C.c_uint32)]
+
+
+class _DiagnoseAssertion(C.Structure):      # struct gs_diagnose_assertion
+    _fields_ = [('index', C.c_uint32), ('reserved', C.c_uint32), ('found', C.c_uint8 * ELT_MAX)]
+
+
 class GsComm(C.Structure):
     """struct gs_comm of include/gstark_comm.h: the table of collectives gs_prover_prove_dist is handed (genstark_amd/comm.py builds them)."""
     _fields_ = [('self', C.c_void_p), ('rank', C.c_int32), ('size', C.c_int32),
@@ -102,6 +112,9 @@ def _driver(backend):
             lib.gs_prover_element_size.restype = C.c_int
             lib.gs_prover_prove_on.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Job), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]
             lib.gs_prover_prove_on.restype = C.c_int
+            lib.gs_prover_diagnose_on.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Job), C.POINTER(_DiagnoseConstraint), C.POINTER(C.c_uint32),
+                                                  C.POINTER(_DiagnoseAssertion), C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_uint64]
+            lib.gs_prover_diagnose_on.restype = C.c_int
             lib.gs_prover_verify_on.argtypes = [C.c_void_p, C.POINTER(_Job), C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
             lib.gs_prover_verify_on.restype = C.c_int
             lib.gs_prover_verify_device_on.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Job), C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
@@ -139,6 +152,13 @@ def _driver(backend):
                 raise GstarkError(f'gs_prover_open failed ({rc}): the ABI library lacks an entry point the driver needs, or computes in another field')
             _bindings[key] = b
         return lib, _bindings[key]
+
+
+def _check_assertions(assertions):
+    if not isinstance(assertions, list):
+        raise TypeError('Assertions parameter must be an array')
+    if len(assertions) == 0:
+        raise TypeError('At least one assertion must be provided')
 
 
 def _is_assembly(air):
@@ -213,27 +233,71 @@ class NativeProver:
             raise GstarkError('the native driver knows the MiMC AIR, GenericAir and AssemblyAir')
         self._shape_args = None      # (declarations, count, shapes) of the AssemblyAir this prover is the inner prover of
 
+    def _inner_prover(self, inputs, seed):
+        """An AssemblyAir's statement as the inner prover sees it: (the NativeProver of the inner AIR of this shape, inputs, seed)."""
+        # initProvingContext(inputs, seed) (lib/Stark.ts:90): the loader lays the inputs out — the inner AIR of this shape, the secret
+        # registers' columns, the first row(s) — and the native driver proves that AIR, writing the inputs' shapes into the proof
+        inner, packed, firsts, shapes = self.stark.air.plan(inputs, seed)
+        nat = self._inner.get(id(inner))
+        if nat is None:
+            if len(self._inner) > 8:
+                self._inner.clear()
+            nat = self._inner[id(inner)] = NativeProver(_Shim(inner, self._exe, self._fri, self._alg))
+        flat = [w for sh in shapes for w in [len(sh)] + list(sh)]
+        nat._shape_args = (self._input_decl, self._ninputs, (C.c_uint32 * max(len(flat), 1))(*flat))
+        return nat, packed, firsts
+
     def prove_bytes(self, assertions, inputs=None, seed=None, comm=None):
         """The serialized proof of Stark.prove(assertions, inputs, seed): stark.serialize(stark.prove(...)) byte for byte.
         comm (a GsComm, genstark_amd/comm.py): ONE proof across the communicator's ranks (gs_prover_prove_dist; every rank calls this
         with the same statement and receives the same bytes)."""
-        stark, air, f = self.stark, self.stark.air, self.field
-        if not isinstance(assertions, list):
-            raise TypeError('Assertions parameter must be an array')
-        if len(assertions) == 0:
-            raise TypeError('At least one assertion must be provided')
-        if _is_assembly(air):
-            # initProvingContext(inputs, seed) (lib/Stark.ts:90): the loader lays the inputs out — the inner AIR of this shape, the secret
-            # registers' columns, the first row(s) — and the native driver proves that AIR, writing the inputs' shapes into the proof
-            inner, packed, firsts, shapes = air.plan(inputs, seed)
-            nat = self._inner.get(id(inner))
-            if nat is None:
-                if len(self._inner) > 8:
-                    self._inner.clear()
-                nat = self._inner[id(inner)] = NativeProver(_Shim(inner, self._exe, self._fri, self._alg))
-            flat = [w for sh in shapes for w in [len(sh)] + list(sh)]
-            nat._shape_args = (self._input_decl, self._ninputs, (C.c_uint32 * max(len(flat), 1))(*flat))
+        _check_assertions(assertions)
+        if _is_assembly(self.stark.air):
+            nat, packed, firsts = self._inner_prover(inputs, seed)
             return nat.prove_bytes(assertions, packed, firsts, comm=comm)
+        job, _keep = self._prove_job(assertions, inputs, seed)
+        cap = 1 << 22
+        out = self._out        # one output buffer per prover (a lane of a pool has its own prover): no 4 MB allocation + copy per proof
+        n = C.c_uint64()
+        err = C.create_string_buffer(512)
+        if comm is None:
+            rc = self.lib.gs_prover_prove_on(self.binding, self.backend.ctx, C.byref(job), C.cast(out, C.c_void_p), cap, C.byref(n), err, 512)
+        else:
+            rc = self.lib.gs_prover_prove_dist_on(self.binding, self.backend.ctx, C.byref(job), C.byref(comm), C.cast(out, C.c_void_p), cap, C.byref(n), err, 512)
+        if rc:
+            raise StarkError(f'native prove() failed ({rc}): {err.value.decode(errors="replace")}')
+        return C.string_at(out, n.value)
+
+    def diagnose(self, assertions, inputs=None, seed=None):
+        """Why the statement prove_bytes(assertions, inputs, seed) takes does not prove — or that it does (gs_prover_diagnose,
+        include/gstark_diagnose.h): {'assertions': [{index, found}], 'constraints': [{violations, firstStep, ...}], 'steps'} in the
+        driver's terms; genstark_amd/diagnose.py makes the Diagnosis of it.  No hash, no queries, no proof."""
+        _check_assertions(assertions)
+        if _is_assembly(self.stark.air):
+            nat, packed, firsts = self._inner_prover(inputs, seed)
+            return nat.diagnose(assertions, packed, firsts)
+        if self.backend.name == 'hip-gfx950' and not hasattr(self.backend.lib, 'gs_nonzero_spans'):
+            raise GstarkError('diagnose: the library has no gs_nonzero_spans (include/gstark_diagnose.h)')
+        job, _keep = self._prove_job(assertions, inputs, seed)
+        es, nc = self.field.elementSize, len(self.degrees)
+        crec = (_DiagnoseConstraint * max(nc, 1))()
+        arec = (_DiagnoseAssertion * len(assertions))()
+        ncons, nbad = C.c_uint32(), C.c_uint32()
+        err = C.create_string_buffer(512)
+        rc = self.lib.gs_prover_diagnose_on(self.binding, self.backend.ctx, C.byref(job), crec, C.byref(ncons), arec, len(assertions), C.byref(nbad), err, 512)
+        if rc:
+            raise StarkError(f'native diagnose() failed ({rc}): {err.value.decode(errors="replace")}')
+        value = lambda raw: int.from_bytes(bytes(raw[:es]), 'little')
+        return {'steps': self.stark.air.steps,
+                'assertions': [{'index': int(arec[i].index), 'found': value(arec[i].found)} for i in range(nbad.value)],
+                'constraints': [{'index': i, 'violations': int(c.violations), 'firstStep': int(c.first_step), 'lastStep': int(c.last_step),
+                                 'firstValue': value(c.first_value), 'degree': int(c.degree), 'declared': int(c.declared), 'limit': int(c.limit),
+                                 'needed': int(c.needed), 'atLeast': bool(c.at_least), 'allZero': bool(c.all_zero)}
+                                for i, c in enumerate(crec[:ncons.value])]}
+
+    def _prove_job(self, assertions, inputs=None, seed=None):
+        """the statement as prove()'s gs_prover_job, and the objects its pointers refer to (keep them for as long as the job is used)"""
+        stark, air, f = self.stark, self.stark.air, self.field
         job = _Job()
         job.steps, job.extension_factor = air.steps, air.extensionFactor
         job.exe_query_count, job.fri_query_count = self._exe, self._fri
@@ -315,17 +379,7 @@ class NativeProver:
             ja.first_rows = first
             ja.segments, ja.segment_len = (nrows, air.segmentLength) if air.segmentLength else (0, 0)
             keep += [t_code, e_code, consts, svals, periods, lens, first]
-        cap = 1 << 22
-        out = self._out        # one output buffer per prover (a lane of a pool has its own prover): no 4 MB allocation + copy per proof
-        n = C.c_uint64()
-        err = C.create_string_buffer(512)
-        if comm is None:
-            rc = self.lib.gs_prover_prove_on(self.binding, self.backend.ctx, C.byref(job), C.cast(out, C.c_void_p), cap, C.byref(n), err, 512)
-        else:
-            rc = self.lib.gs_prover_prove_dist_on(self.binding, self.backend.ctx, C.byref(job), C.byref(comm), C.cast(out, C.c_void_p), cap, C.byref(n), err, 512)
-        if rc:
-            raise StarkError(f'native prove() failed ({rc}): {err.value.decode(errors="replace")}')
-        return C.string_at(out, n.value)
+        return job, keep
 
     def verify_bytes(self, assertions, data, publicInputs=None, device=False):
         """Stark.verify(assertions, stark.parse(data), publicInputs) natively (csrc/verifier.h: lib/Stark.ts:167-248 +

@@ -52,6 +52,12 @@ class Prover:
         """The proof object of lib/Stark.ts:157-162 (parsed from the driver's bytes)."""
         return self.serializer.parseProof(self.prove_bytes(assertions, inputs, seed, comm=comm))
 
+    def diagnose(self, assertions, inputs=None, seed=None):
+        """Why prove(assertions, inputs, seed) would fail, or that it would not (genstark_amd/diagnose.py: Diagnosis): which assertions the
+        trace does not meet, which constraints are violated at which steps, which declared degrees are too low.  Makes no proof."""
+        from .diagnose import from_native
+        return from_native(self._native.diagnose(assertions, inputs, seed), assertions, self.air.field.modulus)
+
     def pack_seed(self, seed):
         """The statement's first rows in the driver's wire form, packed once for many proofs (native.PackedSeed; generic AIRs)."""
         return self._native.pack_seed(seed)

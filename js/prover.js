@@ -82,6 +82,37 @@ function proveAssemblySerialized(assemblyAir, options, assertions, inputs, seed)
     job.inputShapes = [].concat(...context.inputShapes.map(sh => [sh.length].concat(sh)));
     return context.air.field.lib.proveGenericSerialized(context.air.field.ctx, driverPath(context.air.field), job);
 }
+
+// Why a statement does not prove — or that it does (include/gstark_diagnose.h: gs_prover_diagnose, DESIGN.md 3.13): the arguments of the
+// prove functions above minus the hash and the queries (none is made), no proof.  -> { ok, assertions: [{index, step, register, expected,
+// found}], constraints: [{index, violations, firstStep, lastStep, firstValue, degree, declared, limit, needed, atLeast, allZero}] }, values
+// as BigInt — the fields of the Python host's Diagnosis (genstark_amd/diagnose.py).
+const DIAGNOSE_OPTIONS = { hashAlgorithm: 'sha256', exeQueryCount: 1, friQueryCount: 1 };      // (the job's fields the diagnosis does not read)
+function diagnosis(f, raw, assertions) {
+    const bad = raw.assertions.map(a => ({ index: a.index, step: assertions[a.index].step, register: assertions[a.index].register,
+                                           expected: f.mod(assertions[a.index].value), found: a.found }));
+    const ok = bad.length === 0 && raw.constraints.every(c => c.violations === 0 && (c.allZero || c.degree <= c.limit));
+    return { ok, assertions: bad, constraints: raw.constraints };
+}
+function diagnoseGenericSerialized(air, assertions, seed) {
+    const f = air.field;
+    if (!f.lib.diagnoseGenericSerialized) throw new Error('the addon has no diagnoseGenericSerialized: rebuild napi/');
+    if (f.lib.backend === 'hip-gfx950' && !f.lib.has('gs_nonzero_spans'))
+        throw new Error(`the library of the field of ${f.modulus} elements has no gs_nonzero_spans entry point (include/gstark_diagnose.h)`);
+    const context = air.jobContext ? air.jobContext(seed) : air.initProvingContext([], seed);
+    return diagnosis(f, f.lib.diagnoseGenericSerialized(f.ctx, driverPath(f), genericJob(air, context, DIAGNOSE_OPTIONS, assertions)), assertions);
+}
+function diagnoseAssemblySerialized(assemblyAir, assertions, inputs, seed) {
+    if (!assemblyAir.info.inputRegisters) return diagnoseGenericSerialized(assemblyAir.generic, assertions, seed);
+    const context = assemblyAir.initProvingContext(inputs, seed);
+    const f = context.air.field;
+    if (f.lib.backend === 'hip-gfx950' && !f.lib.has('gs_nonzero_spans'))
+        throw new Error(`the library of the field of ${f.modulus} elements has no gs_nonzero_spans entry point (include/gstark_diagnose.h)`);
+    const job = genericJob(context.air, context, DIAGNOSE_OPTIONS, assertions);
+    job.inputRegisters = [].concat(...assemblyAir.info.inputDeclarations.map(declWords));
+    job.inputShapes = [].concat(...context.inputShapes.map(sh => [sh.length].concat(sh)));
+    return diagnosis(f, f.lib.diagnoseGenericSerialized(f.ctx, driverPath(f), job), assertions);
+}
 function verifyAssemblySerialized(assemblyAir, options, assertions, proof, publicInputs, how) {
     if (!(options.hashAlgorithm in HASH_ALG)) throw new TypeError(`Hash algorithm ${options.hashAlgorithm} is not supported`);
     if (!assemblyAir.info.inputRegisters) return verifyGenericSerialized(assemblyAir.generic, options, assertions, proof, how);
@@ -143,4 +174,4 @@ function verifyGenericSerialized(air, options, assertions, proof, how) {
  *  never pays per proof (the Python host's Prover.pack_seed) */
 function packSeed(air, seed) { return air.packSeed(seed); }
 
-module.exports = { packSeed, proveMimcSerialized, proveGenericSerialized, proveAssemblySerialized, verifyMimcSerialized, verifyGenericSerialized, verifyAssemblySerialized };
+module.exports = { packSeed, proveMimcSerialized, proveGenericSerialized, proveAssemblySerialized, diagnoseGenericSerialized, diagnoseAssemblySerialized, verifyMimcSerialized, verifyGenericSerialized, verifyAssemblySerialized };

@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")"
 out=gstark_napi.node
 stale=0
-for d in gstark_napi.cc build.sh ../include/gstark.h ../include/gstark_prover.h; do [ $d -nt $out ] && stale=1; done
+for d in gstark_napi.cc build.sh ../include/gstark.h ../include/gstark_prover.h ../include/gstark_diagnose.h; do [ $d -nt $out ] && stale=1; done
 if [ ! -f $out ] || [ $stale = 1 ]; then
   tmp=$out.tmp.$$
   g++ -O2 -std=c++17 -shared -fPIC -I/usr/include/node gstark_napi.cc -o $tmp -ldl

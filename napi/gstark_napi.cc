@@ -26,6 +26,7 @@
 
 #include "../include/gstark.h"
 #include "../include/gstark_prover.h"
+#include "../include/gstark_diagnose.h"
 
 namespace {
 
@@ -137,6 +138,8 @@ const FnDesc kFns[] = {
     // include/gstark_curve.h: OPTIONAL in the same way; `addends` and `addend_inf` may be 0 (every addend / no addend is infinity)
     {"gs_curve_mul", "cbpupippupp"},
     {"gs_curve_contains", "cbbpup"},
+    // include/gstark_diagnose.h: OPTIONAL in the same way; the three results are host arrays of `rows` uint64 each (Buffers of 8 * rows bytes)
+    {"gs_nonzero_spans", "cpuuuooo"},
     {"gs_pseudorandom_indexes", "biiuio"},
     {"gs_small_eval_poly", "bibio"},
 };
@@ -606,12 +609,63 @@ napi_value ProveMimcSerialized(napi_env env, napi_callback_info info) {
     return buf;
 }
 
+typedef int (*diagnose_on_fn)(const gs_prover_binding *, gs_ctx *, const gs_prover_job *, gs_diagnose_constraint *, uint32_t *, gs_diagnose_assertion *, uint32_t,
+                              uint32_t *, char *, uint64_t);
+static napi_value diagnosis_of(napi_env env, const Driver *drv, const gs_prover_job &job, void *ctx, size_t es) {
+    diagnose_on_fn fn = (diagnose_on_fn)dlsym(drv->dl, "gs_prover_diagnose_on");
+    if (!fn) { napi_throw_error(env, nullptr, "the native driver has no gs_prover_diagnose_on (include/gstark_diagnose.h)"); return nullptr; }
+    std::vector<gs_diagnose_constraint> cons(job.air.nconstraints ? job.air.nconstraints : 1);
+    std::vector<gs_diagnose_assertion> bad(job.nassertions ? job.nassertions : 1);
+    uint32_t ncons = 0, nbad = 0;
+    char err[512] = {0};
+    int rcode = fn(drv->binding, (gs_ctx *)ctx, &job, cons.data(), &ncons, bad.data(), job.nassertions, &nbad, err, sizeof err);
+    if (rcode != GS_OK) { napi_throw_error(env, nullptr, (std::string("native diagnose() failed: ") + err).c_str()); return nullptr; }
+    auto number = [&](napi_value obj, const char *name, uint64_t v) { napi_value x; napi_create_double(env, (double)v, &x); napi_set_named_property(env, obj, name, x); };
+    auto flag = [&](napi_value obj, const char *name, bool v) { napi_value x; napi_get_boolean(env, v, &x); napi_set_named_property(env, obj, name, x); };
+    auto element = [&](napi_value obj, const char *name, const uint8_t *le) {
+        uint64_t words[GS_PROVER_ELT_MAX / 8] = {0};
+        memcpy(words, le, es);
+        napi_value x;
+        napi_create_bigint_words(env, 0, (es + 7) / 8, words, &x);
+        napi_set_named_property(env, obj, name, x);
+    };
+    napi_value out, as, cs;
+    NAPI_OK(env, napi_create_object(env, &out));
+    NAPI_OK(env, napi_create_array_with_length(env, nbad, &as));
+    NAPI_OK(env, napi_create_array_with_length(env, ncons, &cs));
+    for (uint32_t i = 0; i < nbad && i < job.nassertions; i++) {
+        napi_value o;
+        NAPI_OK(env, napi_create_object(env, &o));
+        number(o, "index", bad[i].index);
+        element(o, "found", bad[i].found);
+        napi_set_element(env, as, i, o);
+    }
+    for (uint32_t i = 0; i < ncons; i++) {
+        const gs_diagnose_constraint &c = cons[i];
+        napi_value o;
+        NAPI_OK(env, napi_create_object(env, &o));
+        number(o, "index", i); number(o, "violations", c.violations); number(o, "firstStep", c.first_step); number(o, "lastStep", c.last_step);
+        element(o, "firstValue", c.first_value);
+        number(o, "degree", c.degree); number(o, "declared", c.declared); number(o, "limit", c.limit); number(o, "needed", c.needed);
+        flag(o, "atLeast", c.at_least != 0); flag(o, "allZero", c.all_zero != 0);
+        napi_set_element(env, cs, i, o);
+    }
+    napi_set_named_property(env, out, "assertions", as);
+    napi_set_named_property(env, out, "constraints", cs);
+    return out;
+}
+
 // proveGenericSerialized(ctx, proverLibPath, job) -> Buffer: the same ONE call for an AIR given as register-machine programs (kind 1 of
 // gs_prover_air: what js/air_generic.js holds for the reference's Rescue / Poseidon examples).
 //   job = { steps, extensionFactor, exeQueryCount, friQueryCount, hashAlg, rootOfUnity: Buffer(16), assertions: [...], registers, degrees: number[],
 //           tCode / iCode / eCode: number[] (4 words per instruction), consts: Buffer(16 * nconsts), vmRegs, staticValues: Buffer, staticPeriods: number[],
 //           staticTables: BigInt (device pointer), staticLens: number[], firstRows: Buffer, segments, segmentLen }
-napi_value ProveGenericSerialized(napi_env env, napi_callback_info info) {
+static napi_value generic_one_call(napi_env env, napi_callback_info info, bool diagnose);
+napi_value ProveGenericSerialized(napi_env env, napi_callback_info info) { return generic_one_call(env, info, false); }
+// diagnoseGenericSerialized(ctx, proverLibPath, job) -> { assertions: [{index, found}], constraints: [{...}] }: the job of
+// proveGenericSerialized through gs_prover_diagnose_on (include/gstark_diagnose.h) — no proof; values as BigInt
+napi_value DiagnoseGenericSerialized(napi_env env, napi_callback_info info) { return generic_one_call(env, info, true); }
+static napi_value generic_one_call(napi_env env, napi_callback_info info, bool diagnose) {
     size_t argc = 5;
     napi_value argv[5];
     void *ctx = nullptr;
@@ -748,6 +802,7 @@ napi_value ProveGenericSerialized(napi_env env, napi_callback_info info) {
         as[i].step = step; as[i].reg = (uint32_t)reg; memcpy(as[i].value, val, es);
     }
     job.assertions = as.data(); job.nassertions = na;
+    if (diagnose) return diagnosis_of(env, drv, job, ctx, es);
     if (argc >= 4) return verify_instead(env, drv, argv[3], job, ctx, argc >= 5 ? argv[4] : nullptr);
     static thread_local std::vector<uint8_t> out;      // (kept between calls: a fresh vector of this size is 4 MB of zeroing per proof)
     if (out.size() < (1u << 22)) out.resize(1u << 22);
@@ -861,6 +916,7 @@ napi_value Open(napi_env env, napi_callback_info info) {
         {"merkleProveBatch", nullptr, MerkleProveBatch, nullptr, nullptr, nullptr, napi_default, L},
         {"proveMimcSerialized", nullptr, ProveMimcSerialized, nullptr, nullptr, nullptr, napi_default, L},
         {"proveGenericSerialized", nullptr, ProveGenericSerialized, nullptr, nullptr, nullptr, napi_default, L},
+        {"diagnoseGenericSerialized", nullptr, DiagnoseGenericSerialized, nullptr, nullptr, nullptr, napi_default, L},
     };
     napi_value out;
     NAPI_OK(env, napi_create_object(env, &out));
@@ -871,7 +927,7 @@ napi_value Open(napi_env env, napi_callback_info info) {
 napi_value Init(napi_env env, napi_value exports) {
     const struct { const char *name; napi_callback cb; } fns[] = {
         {"load", Load}, {"open", Open}, {"fieldInfo", FieldInfo}, {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"alloc", Alloc}, {"call", Call}, {"has", Has},
-        {"merkleProveBatch", MerkleProveBatch}, {"proveMimcSerialized", ProveMimcSerialized}, {"proveGenericSerialized", ProveGenericSerialized},
+        {"merkleProveBatch", MerkleProveBatch}, {"proveMimcSerialized", ProveMimcSerialized}, {"proveGenericSerialized", ProveGenericSerialized}, {"diagnoseGenericSerialized", DiagnoseGenericSerialized},
         {"packElements", PackElements}, {"unpackElements", UnpackElements},
     };
     for (auto &f : fns) {
