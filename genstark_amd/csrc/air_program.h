@@ -1,6 +1,6 @@
 // air_program.h — what the native consumers of an AIR program (include/gstark.h, "AIR ... generic straight-line programs") must agree on,
 // stated once: the opcodes, the decoder, the program as one value, the layout of the static registers, the validator and the grouping
-// rule for exponentiations.  For the interpreters of air_vm.hip, the code generator of air_jit.hip and the verifier (verifier.h, built by
+// rule for exponentiations.  For the interpreters of air_vm.hip, the code generator of air_codegen.h and the verifier (verifier.h, built by
 // g++).  Plain C++: no HIP runtime, no context.  What an instruction DOES stays with each interpreter: a shared executor compiled to the
 // same kernel resources and ran the interpreted traces up to 10% slower (profiles/air_program.md).
 #pragma once

@@ -11,18 +11,13 @@
 //   request  "GSJ1" u32 nitems { u32 name_len, name, u64 len, bytes }*  u32 path_len, cache path ("" = none)
 //            item 0: name = kernel entry point, bytes = generated source; items 1..: the field headers the source includes
 //   reply    "GSOK" u64 len, code object   |   "GSER" u64 len, compiler log
+// The compilation itself and the cache file's rules are jit_build.h's, shared with the in-process builds of air_jit.hip.
 // Needs no GPU (hiprtc cross-compiles for gfx950).
-#include <hip/hiprtc.h>
-#include <fcntl.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 #include <sys/socket.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
-#include <string>
-#include <vector>
+#include "jit_build.h"
 
 static bool read_all(void *dst, size_t n) {
     char *p = (char *)dst;
@@ -50,23 +45,6 @@ static void reply(const char *tag, const void *data, uint64_t len) {
     write_all(&len, 8);
     write_all(data, len);
 }
-// same rules as air_jit.hip's jit_disk_write: a new 0600 file of this user, renamed into place
-static void cache_write(const std::string &path, const std::vector<char> &code) {
-    if (path.empty() || code.empty()) return;
-    char tmp[32];
-    snprintf(tmp, sizeof tmp, ".%d.tmp", (int)getpid());
-    const std::string t = path + tmp;
-    const int fd = open(t.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_NOFOLLOW | O_CLOEXEC, 0600);
-    if (fd < 0) return;
-    size_t put = 0;
-    while (put < code.size()) {
-        const ssize_t r = write(fd, code.data() + put, code.size() - put);
-        if (r <= 0) break;
-        put += (size_t)r;
-    }
-    close(fd);
-    if (put == code.size()) rename(t.c_str(), path.c_str()); else remove(t.c_str());
-}
 
 int main() {
     char magic[4];
@@ -87,28 +65,15 @@ int main() {
     std::string path(pl, 0);
     if (pl && !read_all(&path[0], pl)) return 2;
 
-    std::vector<const char *> hn, hb;
-    for (uint32_t i = 1; i < nitems; i++) { hn.push_back(names[i].c_str()); hb.push_back(bodies[i].c_str()); }
-    hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, bodies[0].c_str(), "gs_air_jit.hip", (int)hn.size(), hb.data(), hn.data()) != HIPRTC_SUCCESS) {
-        const char *m = "hiprtcCreateProgram failed";
-        reply("GSER", m, strlen(m));
-        return 1;
-    }
-    const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
-    if (hiprtcCompileProgram(prog, 3, opts) != HIPRTC_SUCCESS) {
-        size_t ls = 0;
-        hiprtcGetProgramLogSize(prog, &ls);
-        std::string log(ls, 0);
-        if (ls) hiprtcGetProgramLog(prog, &log[0]);
+    JitHeaders headers;
+    for (uint32_t i = 1; i < nitems; i++) headers.push_back({names[i], bodies[i].c_str()});
+    std::vector<char> code;
+    std::string log;
+    if (!jit_build(bodies[0], headers, code, log)) {
         reply("GSER", log.data(), log.size());
         return 1;
     }
-    size_t cs = 0;
-    hiprtcGetCodeSize(prog, &cs);
-    std::vector<char> code(cs);
-    hiprtcGetCode(prog, code.data());
-    cache_write(path, code);                    // first: the host may be gone by now, the next process still finds the program
+    jit_cache_write(path, code);                // first: the host may be gone by now, the next process still finds the program
     reply("GSOK", code.data(), code.size());
     return 0;
 }

@@ -1,6 +1,6 @@
 """AIR programs for the register machine of include/gstark.h, with a model of that machine on Python integers.
 
-The machine has four native implementations, each with optimisations of its own (the code generator of csrc/air_jit.hip, the device
+The machine has four native implementations, each with optimisations of its own (the code generator of csrc/air_codegen.h, the device
 interpreters of csrc/air_vm.hip, its host_run and the verifier's run_program) beside the oracle's loop; what they must agree on before
 they run — opcodes, validator, static layout, grouping rule — is stated once in csrc/air_program.h.  This module holds what
 tests/test_air_programs.py and tests/test_air_program_header.py compare them with and on:
@@ -18,7 +18,7 @@ from conftest import rand_elements
 from field_corners import FIXED, cases_for, edge_list, product_pairs
 
 LOADC, LOADR, LOADN, LOADS, ADD, SUB, MUL, POW, POWC, OUT = range(10)
-FLAVOURS = {name: FIXED[name] for name in ('p128', 'q64', 'p224')}       # name -> (modulus, bits)
+FLAVOURS = {name: FIXED[name] for name in ('p128', 'q64', 'p224')}       # name -> (modulus, bits): the flavours the device tests run (the builders take any of FIXED)
 HOST_SEGMENTS = 8           # GS_HOST_TRACE_MAX_SEGMENTS: traces of at most this many segments run on a host core, whatever the JIT mode
 
 
@@ -379,7 +379,7 @@ def shape_program(q, bits, vm_regs, registers, segment_counts=(9,), seglen=3):
 
 def targeted_programs(name):
     """Every targeted trace program of one field flavour, in a fixed order."""
-    q, bits = FLAVOURS[name]
+    q, bits = FIXED[name]
     progs = [rows_program(q, bits)] + [lanes_program(q, bits, w) for w in (1, 2, 4, 5, 12)]
     progs += [rounds_program(q, bits), short_exponents_program(q, bits), long_exponents_program(q, bits), pow_groups_program(q, bits),
               statics_program(q, bits), outputs_program(q, bits), two_outs_program(q, bits), init_program(q, bits, 4), init_program(q, bits, 1),
@@ -437,7 +437,7 @@ def constraint_program(q, bits, fused, nc, pstride, shift, vm_regs):
 
 
 def constraint_programs(name):
-    q, bits = FLAVOURS[name]
+    q, bits = FIXED[name]
     return [constraint_program(q, bits, fused, *shape) for shape in CONSTRAINT_SHAPES for fused in (True, False)]
 
 
@@ -445,7 +445,7 @@ def constraint_programs(name):
 def generated_program(seed, name):
     """A random program at instruction level: expression DAGs over every opcode, biased toward sums of products by constants (rows fuse)
     and repeated exponents (groups form).  Every third seed is a constraint program (LOADN), the others are trace programs."""
-    q, bits = FLAVOURS[name]
+    q, bits = FIXED[name]
     rng = random.Random(seed * 7919 + bits)
     constraints = seed % 3 == 2
     regs = rng.randint(1, 8)

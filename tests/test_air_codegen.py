@@ -1,4 +1,4 @@
-"""The code generator of csrc/air_jit.hip, checked where there is no GPU: gs_air_jit_check turns an AIR program into HIP source and
+"""The code generator of csrc/air_codegen.h, checked where there is no GPU: gs_air_jit_check turns an AIR program into HIP source and
 runs the compiler (hiprtc cross-compiles gfx950 without a device) — the "does it build" tier for what a serving prover compiles at
 run time.  The values the compiled programs compute are compared with the interpreter's in the gpu tier
 (test_generic_air.py::test_compiled_air_programs_equal_interpreted, test_pipeline.py; test_air_programs.py for programs written for
@@ -63,7 +63,7 @@ def generated_trace_source(air, lib, tmp_path, monkeypatch):
 
 
 def test_trace_kernels_spread_products_over_lanes(oracle_backend, hip_libs, tmp_path, monkeypatch):
-    """Shape of the generated trace kernels (csrc/air_jit.hip): products of one depth share a round over the lanes of
+    """Shape of the generated trace kernels (csrc/air_codegen.h): products of one depth share a round over the lanes of
     a segment's group; S-box layers are one member per lane; operands are picked limb-wise (never `if (sub == i) x = v`, which the
     compiler turns into scratch traffic); the lanes exchange results through LDS."""
     f = PrimeField(backend=oracle_backend)

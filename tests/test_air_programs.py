@@ -1,4 +1,4 @@
-"""What compiled and interpreted AIR programs COMPUTE, on programs written for every branch of the code generator (csrc/air_jit.hip)
+"""What compiled and interpreted AIR programs COMPUTE, on programs written for every branch of the code generator (csrc/air_codegen.h)
 and of the interpreters (csrc/air_vm.hip), and on generated ones.  The reference is a model of the register machine of include/gstark.h
 on Python integers (tests/air_programs.py); all of it is integer work, so every comparison is on equality.
 

@@ -153,7 +153,7 @@ def test_products(lib, terms):
 
 def test_square_and_exponentiation_chain(lib):
     """lz_sqr on NN inputs (ends of the limb intervals included) and k squarings + one product with no packing in between — what the
-    long exponentiations of compiled AIR programs are made of (csrc/air_jit.hip: emit_pow)"""
+    long exponentiations of compiled AIR programs are made of (csrc/air_codegen.h: emit_pow)"""
     rng = random.Random(123)
     n = 6000
     xs = [rand_nn(rng, extreme=(i % 2 == 0)) for i in range(n)]
