@@ -178,6 +178,20 @@ _TREE_VERIFY_SIGNATURES = {
 }
 TREE_VERIFY_SYMBOLS = tuple(_TREE_VERIFY_SIGNATURES)
 
+# include/gstark_sparse_tree.h: sparse trees of fixed depth on the device, for both families; optional in the same way
+# (genstark_amd/sparse_tree.py keeps the tree on host integers where a library lacks the family)
+_SPARSE_TREE_SIGNATURES = {
+    'gs_hades_sparse_create': (_int, [_vp, _vp, _u32, _u32, _bytes, _u64, _pvp]),
+    'gs_rescue_sparse_create': (_int, [_vp, _vp, _u32, _bytes, _u64, _pvp]),
+    'gs_sparse_update': (_int, [_vp, _vp, C.POINTER(_u64), _vp, _u64, _vp, _vp]),
+    'gs_sparse_paths': (_int, [_vp, _vp, C.POINTER(_u64), _u64, _vp]),
+    'gs_sparse_root': (_int, [_vp, _vp, _vp]),
+    'gs_sparse_empties': (_int, [_vp, _vp, _vp]),
+    'gs_sparse_stored': (_u64, [_vp, _u32]),
+    'gs_sparse_destroy': (_int, [_vp, _vp]),
+}
+SPARSE_TREE_SYMBOLS = tuple(_SPARSE_TREE_SIGNATURES)
+
 # include/gstark_mimc.h: gs_mimc_composition from per-point tables built before the trace; optional in the same way (a driver bound to a
 # library without them calls gs_mimc_composition)
 _MIMC_SIGNATURES = {
@@ -217,7 +231,7 @@ def load_library(path):
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
-                              + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
+                              + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_SPARSE_TREE_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
                               + list(_CURVE_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:

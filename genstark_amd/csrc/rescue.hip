@@ -25,9 +25,11 @@
 //               only (k_rescue_path_roots<G>: a group of G lanes per path, every level in ONE launch); the entry's cap is form 2's limit.
 #include "sponge_common.h"
 #include "tree_update.h"
+#include "sparse_tree.h"
 #include "tree_verify.h"
 #include "../../include/gstark_rescue.h"
 #include "../../include/gstark_tree_update.h"
+#include "../../include/gstark_sparse_tree.h"
 #include "../../include/gstark_tree_verify.h"
 #if defined(GS_FIELD_128)
 #include "gf128_lazy.h"
@@ -361,6 +363,7 @@ int gs_rescue_create(gs_ctx *c, uint32_t width, uint32_t rounds, uint64_t alpha,
     if (rc) return rc;
     fe *consts = (fe *)p;
     *out = new gs_rescue{c, width, rounds, alpha, (uint32_t)best.size(), best_table, best_cost, sponge_pow_products(alpha), consts, (const uint32_t *)(consts + nkeys + nmds)};
+    sponge_register(*out);
     return GS_OK;
 }
 
@@ -407,6 +410,19 @@ int gs_rescue_merkle_update(gs_ctx *c, const gs_rescue *h, void *nodes, uint64_t
         traffic(c, h, cnt, 2, 1, 1, form);
         return launch_hash(c, h, rows, cnt, 2, 1, 1, form, out);
     });
+}
+
+// the tree's kernels and its other entries (gs_sparse_*) are family-neutral and live in hades.hip
+int gs_rescue_sparse_create(gs_ctx *c, const gs_rescue *h, uint32_t depth, const void *empty_leaf_host, uint64_t slots_hint, gs_sparse **tree) {
+    int rc;
+    if (c && h && !sponge_serial(h)) return gs_fail(c, GS_ERR_ARG, "rescue_sparse_create: the hash has been destroyed");
+    if ((rc = sponge_check_handle(c, h, "rescue_sparse_create"))) return rc;
+    if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_sparse_create: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
+    return sparse_tree_create(c, "rescue_sparse_create", h, depth, 1, empty_leaf_host, slots_hint, [c, h](const fe *rows, uint64_t cnt, fe *out) {
+        const uint32_t form = pick_form(cnt, 0);
+        traffic(c, h, cnt, 2, 1, 1, form);
+        return launch_hash(c, h, rows, cnt, 2, 1, 1, form, out);
+    }, tree);
 }
 
 int gs_rescue_merkle_path_roots(gs_ctx *c, const gs_rescue *h, const void *paths, uint32_t depth, const uint64_t *indexes_host, const void *leaves, uint64_t count,

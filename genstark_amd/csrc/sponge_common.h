@@ -10,6 +10,8 @@
 #include "common.h"
 
 #include <initializer_list>
+#include <mutex>
+#include <unordered_map>
 
 #define GS_SPONGE_WIDTHS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)        // the state widths a unit instantiates: switch (width) { GS_SPONGE_WIDTHS(X) }
 
@@ -81,11 +83,42 @@ static inline int sponge_upload(gs_ctx *c, std::initializer_list<sponge_part> pa
     return rc;
 }
 
+// The live parameter handles of both units, each with the serial number it was created under: what outlives a handle and keeps its
+// pointer (a sparse tree, sparse_tree.h) asks here before it dereferences it, so a destroyed hash is an error code and not a read of
+// freed memory.  One registry per library: a function-local static of an inline function.
+struct sponge_registry {
+    std::mutex mutex;
+    std::unordered_map<const void *, uint64_t> live;
+    uint64_t next = 1;
+};
+inline sponge_registry &sponge_handles() {
+    static sponge_registry registry;
+    return registry;
+}
+static inline uint64_t sponge_register(const void *h) {
+    sponge_registry &r = sponge_handles();
+    std::lock_guard<std::mutex> lock(r.mutex);
+    return r.live[h] = r.next++;
+}
+static inline void sponge_unregister(const void *h) {
+    sponge_registry &r = sponge_handles();
+    std::lock_guard<std::mutex> lock(r.mutex);
+    r.live.erase(h);
+}
+// the serial of a live handle; 0: never created, or destroyed
+static inline uint64_t sponge_serial(const void *h) {
+    sponge_registry &r = sponge_handles();
+    std::lock_guard<std::mutex> lock(r.mutex);
+    const auto it = r.live.find(h);
+    return it == r.live.end() ? 0 : it->second;
+}
+
 template <class H>
 static inline int sponge_destroy(gs_ctx *c, H *h, const char *who) {
     if (!c || !h) return c ? GS_OK : GS_ERR_ARG;
     const int rc = sponge_check_handle(c, h, who);
     if (rc) return rc;
+    sponge_unregister(h);
     gs_free(c, h->consts);                                                   // parked in the context's cache: launches already queued still read it in order
     delete h;
     return GS_OK;

@@ -212,3 +212,14 @@ def poseidon_tree(field, leaves):
     cols = round_constant_columns(field)
     rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
     return HadesMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, STATE_WIDTH, rc, MDS), leaves, 2)
+
+
+def poseidon_sparse_tree(field, depth, empty=None, slots_hint=1024):
+    """The sparse tree of 2^depth leaves (depth 1 .. 36) over the same hash (genstark_amd/sparse_tree.py: HadesSparseMerkleTree): every
+    leaf holds `empty` (default: zeros) until set, and root, paths and update records are those of poseidon_tree(field, [empty] * 2^depth).
+    Its records feed compute_merkle_update_air(field, depth) at depths no dense tree can hold."""
+    from .hades import HadesHash
+    from .sparse_tree import HadesSparseMerkleTree
+    cols = round_constant_columns(field)
+    rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
+    return HadesSparseMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, STATE_WIDTH, rc, MDS), depth, 2, empty, slots_hint)

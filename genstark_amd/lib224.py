@@ -253,3 +253,14 @@ def verify_schnorr_signature_air(field, count=1, extensionFactor=16):
     air.expandInputs = expand
     air.segmentSeeds = lambda raw: [[raw[0][s], raw[1][s], raw[3][s], raw[4][s], raw[6][s], raw[7][s]] for s in range(count)]
     return air
+
+
+def poseidon_sparse_tree(field, depth, empty=None, slots_hint=1024):
+    """The sparse tree of 2^depth leaves (depth 1 .. 36) over the same hash (genstark_amd/sparse_tree.py: HadesSparseMerkleTree): every
+    leaf holds `empty` (default: zeros) until set, and root, paths and update records are those of poseidon_tree(field, [empty] * 2^depth).
+    Its records feed compute_merkle_update_air(field, depth) at depths no dense tree can hold."""
+    from .hades import HadesHash
+    from .sparse_tree import HadesSparseMerkleTree
+    cols = round_constant_columns(field)
+    rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
+    return HadesSparseMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, WIDTH, rc, MDS), depth, 1, empty, slots_hint)

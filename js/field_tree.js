@@ -3,7 +3,8 @@
 // when its owner is collected, one permutation per row of a device Matrix, and the heap-layout Merkle tree of nodes of `digest` field
 // elements with its paths (the gather is the family-neutral gs_hades_merkle_paths: it reads nothing but the node array) and its batched
 // updates (include/gstark_tree_update.h: update / updateMany return every update's witness), and the consuming side of both
-// (include/gstark_tree_verify.h: static pathRoots / verifyMany / verifyUpdates check batches of paths and update records in one launch).
+// (include/gstark_tree_verify.h: static pathRoots / verifyMany / verifyUpdates check batches of paths and update records in one launch),
+// and the sparse tree of fixed depth over the same node functions (include/gstark_sparse_tree.h: SparseDeviceTree).
 const { Matrix, Vector } = require('./galois.js');
 
 /** a registry that destroys the handle of a collected owner through `symbol` (null where the engine has none) */
@@ -104,6 +105,94 @@ class DeviceTree {
     }
 }
 
+/** throws when the field's library lacks `symbol` of include/gstark_sparse_tree.h (optional in the same way) */
+function needSparse(field, symbol) {
+    if (!field.lib.has || !field.lib.has(symbol)) {
+        throw new Error(`the library of the field of ${field.modulus} elements has no ${symbol} entry point (include/gstark_sparse_tree.h): sparse trees are not kept on this device library`);
+    }
+}
+
+const sparseRegistry = destroyRegistry('gs_sparse_destroy');
+
+/** The sparse tree of 2^depth leaves (depth 1 .. 36) that all hold `empty` (default: zeros) until set: root, paths and update records are
+ *  those of the dense tree over [empty] * 2^depth.  Only nodes with something set below them are stored on the device (each stored leaf
+ *  costs up to `depth` stored nodes and host index entries; the store doubles from slotsHint slots, never past 2^31; nothing is pruned).
+ *  Indexes are Numbers or BigInts below 2^depth; at most 2^20 updates or paths per call.  A path of an index never set starts with
+ *  `empty`.  There is no `stored` member: gs_sparse_stored returns a count, not a status, and the addon's call() delivers statuses only
+ *  (Python has it).  family: { symbol, create(handle, depth, emptyBytes, slotsHint, out) } — the family's create entry.  There is no host
+ *  fallback: a missing entry throws an Error that names it. */
+class SparseDeviceTree {
+    constructor(field, hash, depth, digest, empty, slotsHint, family) {
+        for (const symbol of [family.symbol, 'gs_sparse_update', 'gs_sparse_paths', 'gs_sparse_root', 'gs_sparse_empties', 'gs_sparse_destroy']) needSparse(field, symbol);
+        if (!(Number.isInteger(depth) && depth >= 1 && depth <= 36)) throw new Error(`a depth of 1 .. 36, not ${depth}`);
+        if (!(Number.isInteger(slotsHint) && slotsHint >= 1 && slotsHint <= 2 ** 31)) throw new Error(`slotsHint is 1 .. 2^31, not ${slotsHint}`);
+        let row = new Array(digest).fill(0n);
+        if (empty !== undefined && empty !== null) row = digest === 1 && !Array.isArray(empty) ? [empty] : empty;
+        if (!Array.isArray(row) || row.length !== digest || row.some(v => typeof v !== 'bigint')) throw new Error(`the empty leaf has ${digest} element${digest > 1 ? 's' : ''} (BigInts)`);
+        this.field = field; this.hash = hash; this.depth = depth; this.digest = digest; this.leafCount = 2 ** depth;
+        const out = Buffer.alloc(8);
+        family.create(hash.handle(), depth, field.packLe(row.map(v => field.mod(v))), slotsHint, out);
+        this._tree = out.readBigUInt64LE(0);
+        if (sparseRegistry) sparseRegistry.register(this, { lib: field.lib, ctx: field.ctx, handle: this._tree });
+        this._empties = null;
+    }
+    _shape(row) { return this.digest === 1 ? row[0] : row; }
+    _nodes(row) { const out = []; for (let l = 0; l * this.digest < row.length; l++) out.push(this._shape(row.slice(l * this.digest, (l + 1) * this.digest))); return out; }
+    /** indexes as BigInts (anything above 2^32 survives the trip to the library) */
+    _indexes(indexes, what) {
+        if (indexes.length > 2 ** 20) throw new Error(`at most 2^20 ${what} per call, not ${indexes.length}`);
+        return indexes.map(i => {
+            const ok = typeof i === 'bigint' || Number.isSafeInteger(i), v = ok ? BigInt(i) : -1n;
+            if (v < 0n || v >> BigInt(this.depth)) throw new Error(`index ${i} is outside of the 2^${this.depth} leaves`);
+            return v;
+        });
+    }
+    get root() {
+        const out = new Matrix(this.field, 1, this.digest);
+        this.field.lib.call('gs_sparse_root', this.field.ctx, this._tree, out.ptr);
+        return this._shape(out.toValues()[0]);
+    }
+    /** empties[0 .. depth]: the node of every level above nothing but empty leaves */
+    get empties() {
+        if (this._empties === null) {
+            const out = new Matrix(this.field, this.depth + 1, this.digest);
+            this.field.lib.call('gs_sparse_empties', this.field.ctx, this._tree, out.ptr);
+            this._empties = out.toValues().map(r => this._shape(r));
+        }
+        return this._empties.slice();
+    }
+    get(index) { return this.prove(index)[0]; }
+    prove(index) { return this.proveMany([index])[0]; }
+    /** prove(index) for every index, set or not: one launch, one read-back; device = true: the Matrix of one row per path, which the static
+     *  pathRoots / verifyMany take without a read-back */
+    proveMany(indexes, device = false) {
+        const idx = this._indexes(indexes, 'paths'), out = new Matrix(this.field, idx.length, (this.depth + 1) * this.digest);
+        if (idx.length) this.field.lib.call('gs_sparse_paths', this.field.ctx, this._tree, idx, idx.length, out.ptr);
+        if (device) return out;
+        return idx.length ? out.toValues().map(r => this._nodes(r)) : [];
+    }
+    update(index, leaf) { return this.updateMany([index], [leaf])[0]; }
+    /** sets leaf indexes[j] to leaves[j], j = 0, 1, .. in that order (repeats allowed); per update { before, root } as DeviceTree.updateMany */
+    updateMany(indexes, leaves) {
+        const idx = this._indexes(indexes, 'updates'), count = idx.length;
+        let src = leaves;
+        if (Array.isArray(leaves)) {
+            if (leaves.length !== count) throw new Error(`${count} indexes and ${leaves.length} leaves: an update is one of each`);
+            if (!count) return [];
+            if (leaves.some(v => (Array.isArray(v) ? v.length : 1) !== this.digest || (this.digest > 1) !== Array.isArray(v))) throw new Error(`the leaves have ${this.digest} element${this.digest > 1 ? 's' : ''} each`);
+            src = this.field.newMatrixFrom(this.digest === 1 ? leaves.map(v => [v]) : leaves);
+        }
+        this.field._own(src);
+        if ((src instanceof Vector ? src.length : src.rowCount) !== count) throw new Error(`${count} indexes and ${src instanceof Vector ? src.length : src.rowCount} leaves: an update is one of each`);
+        if ((src instanceof Vector ? 1 : src.colCount) !== this.digest) throw new Error(`the leaves have ${this.digest} element${this.digest > 1 ? 's' : ''} each`);
+        if (!count) return [];
+        const before = new Matrix(this.field, count, (this.depth + 1) * this.digest), roots = new Matrix(this.field, count, this.digest);
+        this.field.lib.call('gs_sparse_update', this.field.ctx, this._tree, idx, src.ptr, count, before.ptr, roots.ptr);
+        const values = before.toValues(), after = roots.toValues();
+        return idx.map((_, j) => ({ before: this._nodes(values[j]), root: this._shape(after[j]) }));
+    }
+}
+
 /** a path (the leaf, then its siblings bottom-up) against a root: node(left, right) level by level, sides by the index bits */
 function verifyPath(root, index, proof, node, same = (a, b) => a === b) {
     let v = proof[0];
@@ -178,4 +267,4 @@ function installVerify(cls, family) {
     };
 }
 
-module.exports = { destroyRegistry, needDevice, needUpdate, needVerify, lazyHandle, hashMany, DeviceTree, verifyPath, installVerify };
+module.exports = { destroyRegistry, needDevice, needUpdate, needVerify, needSparse, lazyHandle, hashMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify };

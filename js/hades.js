@@ -9,7 +9,7 @@
 // library lacks the entry points (they are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const crypto = require('crypto');
 const { Matrix, Vector } = require('./galois.js');
-const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, verifyPath, installVerify } = require('./field_tree.js');
+const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify } = require('./field_tree.js');
 
 function constants(field, seed, count) {      // utils.ts:115-122
     const out = new Array(count);
@@ -96,10 +96,31 @@ class MerkleTree2 extends HadesTree {     // utils.ts:169-210: nodes of one elem
     static verify(root, index, proof, hash) { return verifyPath(root, index, proof, (left, right) => hash([left, right])[0]); }
 }
 
+/** the sparse tree of 2^depth leaves (depth 1 .. 36) over the same node function (include/gstark_sparse_tree.h; js/field_tree.js) */
+class HadesSparseTree extends SparseDeviceTree {
+    constructor(depth, hash, digest, empty, slotsHint = 1024) {
+        const field = hash && hash.field;
+        if (!field || !hash.handle) throw new Error('the hash function must come from createHash of js/hades.js');
+        if (2 * digest >= hash.stateWidth) throw new Error(`nodes of ${digest} elements: two of them do not fit a state of ${hash.stateWidth} beside its capacity`);
+        super(field, hash, depth, digest, empty, slotsHint, { symbol: 'gs_hades_sparse_create', create: (handle, d, emptyBytes, hint, out) =>
+            field.lib.call('gs_hades_sparse_create', field.ctx, handle, d, digest, emptyBytes, hint, out) });
+    }
+}
+
+class SparseMerkleTree extends HadesSparseTree {      // the shape of MerkleTree: nodes of two elements
+    constructor(depth, hash, empty, slotsHint) { super(depth, hash, 2, empty, slotsHint); }
+    static verify(root, index, proof, hash) { return MerkleTree.verify(root, index, proof, hash); }
+}
+
+class SparseMerkleTree2 extends HadesSparseTree {     // the shape of MerkleTree2: nodes of one element
+    constructor(depth, hash, empty, slotsHint) { super(depth, hash, 1, empty, slotsHint); }
+    static verify(root, index, proof, hash) { return MerkleTree2.verify(root, index, proof, hash); }
+}
+
 // static pathRoots(hash, indexes, proofs, leaves?), verifyMany(root, indexes, proofs, hash), verifyUpdates(oldRoot, indexes, leaves, records, hash)
-for (const [cls, digest] of [[MerkleTree, 2], [MerkleTree2, 1]]) {
+for (const [cls, digest] of [[MerkleTree, 2], [MerkleTree2, 1], [SparseMerkleTree, 2], [SparseMerkleTree2, 1]]) {
     installVerify(cls, { digest, symbol: 'gs_hades_merkle_path_roots', call: (field, handle, paths, depth, indexes, leaves, count, roots) =>
         field.lib.call('gs_hades_merkle_path_roots', field.ctx, handle, paths.ptr, depth, digest, indexes, leaves, count, roots.ptr) });
 }
 
-module.exports = { createHash, getRoundConstants, getMdsMatrix, MerkleTree, MerkleTree2 };
+module.exports = { createHash, getRoundConstants, getMdsMatrix, MerkleTree, MerkleTree2, SparseMerkleTree, SparseMerkleTree2 };

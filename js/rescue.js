@@ -8,7 +8,7 @@
 // batches of paths and of update records checked on the device).  `field` is a PrimeField of js/galois.js.  A field whose library lacks the entry points (they
 // are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const { Vector } = require('./galois.js');
-const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, verifyPath, installVerify } = require('./field_tree.js');
+const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify } = require('./field_tree.js');
 
 const registry = destroyRegistry('gs_rescue_destroy');
 const needDevice = field => needDeviceOf(field, 'rescue', 'Rescue');
@@ -97,6 +97,8 @@ function createRescue(field, alpha, invAlpha, registers, rounds, mds, constants)
             return hashMany(field, 'gs_rescue_hash', rescue.handle(), rows, digest, modified ? 1 : 0, form);
         },
         merkleTree(values) { return new MerkleTree(values, rescue); },
+        /** the sparse tree of 2^depth leaves (depth 1 .. 36) that all hold `empty` until set (include/gstark_sparse_tree.h) */
+        sparseMerkleTree(depth, empty, slotsHint) { return new SparseMerkleTree(depth, rescue, empty, slotsHint); },
     };
     return rescue;
 }
@@ -119,8 +121,20 @@ class MerkleTree extends DeviceTree {      // utils.ts:232-273, built by the dev
     static verify(root, index, proof, hash) { return verifyPath(root, index, proof, hash); }
 }
 
+class SparseMerkleTree extends SparseDeviceTree {      // the sparse form of MerkleTree: nodes of one element
+    constructor(depth, rescue, empty, slotsHint = 1024) {
+        const field = rescue && rescue.field;
+        if (!field || !rescue.handle) throw new Error('the hash must come from createRescue of js/rescue.js');
+        if (rescue.registers < 3) throw new Error(`two nodes do not fit a state of ${rescue.registers} beside its capacity (3 .. 8 registers)`);
+        super(field, rescue, depth, 1, empty, slotsHint, { symbol: 'gs_rescue_sparse_create', create: (handle, d, emptyBytes, hint, out) =>
+            field.lib.call('gs_rescue_sparse_create', field.ctx, handle, d, emptyBytes, hint, out) });
+        this.rescue = rescue;
+    }
+    static verify(root, index, proof, hash) { return verifyPath(root, index, proof, hash); }
+}
+
 // static pathRoots(rescue, indexes, proofs, leaves?), verifyMany(root, indexes, proofs, rescue), verifyUpdates(oldRoot, indexes, leaves, records, rescue)
-installVerify(MerkleTree, { digest: 1, symbol: 'gs_rescue_merkle_path_roots', call: (field, handle, paths, depth, indexes, leaves, count, roots) =>
+for (const cls of [MerkleTree, SparseMerkleTree]) installVerify(cls, { digest: 1, symbol: 'gs_rescue_merkle_path_roots', call: (field, handle, paths, depth, indexes, leaves, count, roots) =>
     field.lib.call('gs_rescue_merkle_path_roots', field.ctx, handle, paths.ptr, depth, indexes, leaves, count, roots.ptr) });
 
-module.exports = { createRescue, MerkleTree };
+module.exports = { createRescue, MerkleTree, SparseMerkleTree };

@@ -135,6 +135,16 @@ const FnDesc kFns[] = {
     // include/gstark_tree_verify.h: OPTIONAL in the same way; `leaves` may be 0 (a path then starts from its own leaf)
     {"gs_hades_merkle_path_roots", "cppiixpup"},
     {"gs_rescue_merkle_path_roots", "cppixpup"},
+    // include/gstark_sparse_tree.h: OPTIONAL in the same way; the create entries write the tree (a pointer) into an 8-byte Buffer like
+    // gs_hades_create, the empty leaf is host bytes; indexes travel as an array of Numbers or BigInts (64 bits each).
+    // gs_sparse_stored returns a count, not a status: call() does not deliver it, so it is not listed
+    {"gs_hades_sparse_create", "cpiibuo"},
+    {"gs_rescue_sparse_create", "cpibuo"},
+    {"gs_sparse_update", "cpxpupp"},
+    {"gs_sparse_paths", "cpxup"},
+    {"gs_sparse_root", "cpp"},
+    {"gs_sparse_empties", "cpp"},
+    {"gs_sparse_destroy", "cp"},
     // include/gstark_curve.h: OPTIONAL in the same way; `addends` and `addend_inf` may be 0 (every addend / no addend is infinity)
     {"gs_curve_mul", "cbpupippupp"},
     {"gs_curve_contains", "cbbpup"},
