@@ -19,13 +19,11 @@
 //   tree        node i = element 0 of modifiedSponge(node 2i, node 2i + 1), heap layout: every level is one hash launch over the level
 //               below, ordered by the stream (the level loop of sponge_common.h, down to the root).  Workgroups are one wave in both forms, so a narrow level spreads over many CUs.
 //               Nothing here synchronises between workgroups.
-//   updates     gs_rescue_merkle_update: the shared driver of tree_update.h over launch_hash with the form pick_form chooses, as the
-//               tree build does: an updated node is the node the build computes.
+//   updates,    gs_rescue_merkle_update and gs_rescue_sparse_create hand rescue_node_hash — what a level of the tree build runs:
+//   sparse      launch_hash with the form pick_form chooses — to the drivers of field_tree.h: an updated node is the node the build computes.
 //   path roots  gs_rescue_merkle_path_roots (tree_verify.h): a path is a dependent chain of permutations, so it is walked in form 2
 //               only (k_rescue_path_roots<G>: a group of G lanes per path, every level in ONE launch); the entry's cap is form 2's limit.
-#include "sponge_common.h"
-#include "tree_update.h"
-#include "sparse_tree.h"
+#include "field_tree.h"
 #include "tree_verify.h"
 #include "../../include/gstark_rescue.h"
 #include "../../include/gstark_tree_update.h"
@@ -303,6 +301,18 @@ void traffic(gs_ctx *c, const gs_rescue *h, uint64_t count, uint32_t arity, uint
     else gs_traffic(c, count * (arity + digest) * GS_ELT, count * rescue_products(h, modified), "k_rescue_hash<%u>", h->width);
 }
 
+// the tree_node_hash of this unit (field_tree.h) and a level of its tree build: `count` rows of two nodes (of one element) into `count` nodes
+int rescue_node_hash(gs_ctx *c, const void *handle, uint32_t, const fe *rows, uint64_t count, fe *out) {
+    const gs_rescue *h = (const gs_rescue *)handle;
+    const uint32_t form = pick_form(count, 0);
+    traffic(c, h, count, 2, 1, 1, form);
+    return launch_hash(c, h, rows, count, 2, 1, 1, form, out);
+}
+
+int rescue_check_nodes(gs_ctx *c, const gs_rescue *h, const char *who) {
+    return h->width >= 3 ? GS_OK : gs_fail(c, GS_ERR_ARG, "%s: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", who, h->width);
+}
+
 // the sliding-window schedule of exponent `bits` (most significant first at bits[nb - 1]) for a window of `w` bits: the words, the
 // table size it needs, and what it costs in squarings + products (table included)
 uint64_t window_schedule(const std::vector<uint8_t> &bits, int w, std::vector<uint32_t> &ops, uint32_t &table) {
@@ -385,51 +395,34 @@ int gs_rescue_hash(gs_ctx *c, const gs_rescue *h, const void *in, uint64_t count
 
 int gs_rescue_merkle(gs_ctx *c, const gs_rescue *h, const void *leaves, uint64_t n, void *nodes_out) {
     int rc;
-    if ((rc = sponge_check_handle(c, h, "rescue_merkle")) || (rc = sponge_check_leaves(c, "rescue_merkle", n))) return rc;
-    if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_merkle: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
+    if ((rc = sponge_check_handle(c, h, "rescue_merkle")) || (rc = sponge_check_leaves(c, "rescue_merkle", n)) || (rc = rescue_check_nodes(c, h, "rescue_merkle"))) return rc;
     if (!leaves || !nodes_out) return GS_ERR_ARG;
     fe *nodes = (fe *)nodes_out;
     if (leaves != (const void *)(nodes + n)) GS_HIP(c, hipMemcpyAsync(nodes + n, leaves, n * GS_ELT, hipMemcpyDeviceToDevice, c->stream));
     GS_HIP(c, hipMemsetAsync(nodes, 0, GS_ELT, c->stream));
     uint64_t rest;
-    return sponge_tree_levels(nodes, n, 1, 0, &rest, [&](const fe *below, uint64_t count, fe *level) {
-        const uint32_t form = pick_form(count, 0);
-        traffic(c, h, count, 2, 1, 1, form);
-        return launch_hash(c, h, below, count, 2, 1, 1, form, level);
-    });
+    return sponge_tree_levels(nodes, n, 1, 0, &rest, [&](const fe *below, uint64_t count, fe *level) { return rescue_node_hash(c, h, 1, below, count, level); });
 }
 
 int gs_rescue_merkle_update(gs_ctx *c, const gs_rescue *h, void *nodes, uint64_t n, const uint64_t *indexes_host, const void *leaves, uint64_t count, void *before_out,
                             void *roots_out) {
     int rc;
-    if ((rc = sponge_check_handle(c, h, "rescue_merkle_update"))) return rc;
-    if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_merkle_update: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
+    if ((rc = sponge_check_handle(c, h, "rescue_merkle_update")) || (rc = rescue_check_nodes(c, h, "rescue_merkle_update"))) return rc;
     if ((rc = tree_update_check(c, "rescue_merkle_update", n, count, indexes_host, nodes, leaves, before_out, roots_out)) || !count) return rc;
-    return tree_update_run(c, (fe *)nodes, n, 1, indexes_host, (const fe *)leaves, count, (fe *)before_out, (fe *)roots_out, [&](const fe *rows, uint64_t cnt, fe *out) {
-        const uint32_t form = pick_form(cnt, 0);
-        traffic(c, h, cnt, 2, 1, 1, form);
-        return launch_hash(c, h, rows, cnt, 2, 1, 1, form, out);
-    });
+    return tree_update_run(c, (fe *)nodes, n, 1, indexes_host, (const fe *)leaves, count, (fe *)before_out, (fe *)roots_out, {rescue_node_hash, h});
 }
 
-// the tree's kernels and its other entries (gs_sparse_*) are family-neutral and live in hades.hip
 int gs_rescue_sparse_create(gs_ctx *c, const gs_rescue *h, uint32_t depth, const void *empty_leaf_host, uint64_t slots_hint, gs_sparse **tree) {
     int rc;
     if (c && h && !sponge_serial(h)) return gs_fail(c, GS_ERR_ARG, "rescue_sparse_create: the hash has been destroyed");
-    if ((rc = sponge_check_handle(c, h, "rescue_sparse_create"))) return rc;
-    if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_sparse_create: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
-    return sparse_tree_create(c, "rescue_sparse_create", h, depth, 1, empty_leaf_host, slots_hint, [c, h](const fe *rows, uint64_t cnt, fe *out) {
-        const uint32_t form = pick_form(cnt, 0);
-        traffic(c, h, cnt, 2, 1, 1, form);
-        return launch_hash(c, h, rows, cnt, 2, 1, 1, form, out);
-    }, tree);
+    if ((rc = sponge_check_handle(c, h, "rescue_sparse_create")) || (rc = rescue_check_nodes(c, h, "rescue_sparse_create"))) return rc;
+    return sparse_tree_create(c, "rescue_sparse_create", {rescue_node_hash, h}, depth, 1, empty_leaf_host, slots_hint, tree);
 }
 
 int gs_rescue_merkle_path_roots(gs_ctx *c, const gs_rescue *h, const void *paths, uint32_t depth, const uint64_t *indexes_host, const void *leaves, uint64_t count,
                                 void *roots_out) {
     int rc;
-    if ((rc = sponge_check_handle(c, h, "rescue_merkle_path_roots"))) return rc;
-    if (h->width < 3) return gs_fail(c, GS_ERR_ARG, "rescue_merkle_path_roots: two nodes do not fit a state of %u beside its capacity (width 3 .. 8)", h->width);
+    if ((rc = sponge_check_handle(c, h, "rescue_merkle_path_roots")) || (rc = rescue_check_nodes(c, h, "rescue_merkle_path_roots"))) return rc;
     if ((rc = tree_verify_check(c, "rescue_merkle_path_roots", depth, count, indexes_host, paths, roots_out)) || !count) return rc;
     return tree_verify_run(c, indexes_host, count, [&](const uint64_t *idx) {
         gs_traffic(c, tree_verify_bytes(depth, 1, leaves != nullptr, count), count * depth * rescue_products(h, 1), "k_rescue_path_roots<%u>", spread_group(h));

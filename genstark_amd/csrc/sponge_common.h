@@ -3,8 +3,7 @@
 //   rows    a workgroup's BLOCK rows of `arity` elements are one contiguous run of memory: it is copied into LDS with consecutive lanes
 //           on consecutive elements, then every thread picks its row up from there; the digests leave the same way (GS_SPONGE_HASH_ROWS).
 //   tree    heap layout: the inputs of ALL nodes of one level are the level below, contiguous, in rows of 2 * digest elements — a level
-//           IS a hash launch (sponge_tree_levels).  The path gather reads nothing but a node array in that layout and belongs to no
-//           family: it is defined once, in hades.hip, under the name it was first exported with (gs_hades_merkle_paths).
+//           IS a hash launch (sponge_tree_levels).  What reads and writes nodes and knows no permutation is field_tree.hip.
 // Every message starts with the caller's name (`who`): the texts are those of the entry points.
 #pragma once
 #include "common.h"
@@ -83,8 +82,20 @@ static inline int sponge_upload(gs_ctx *c, std::initializer_list<sponge_part> pa
     return rc;
 }
 
+// A host array that one launch reads: up through the stream-ordered scratch, launch(its device copy), and the scratch goes back at
+// once — the cache is stream-ordered, so the launch still reads it.
+template <class Launch>
+static inline int sponge_with_upload(gs_ctx *c, const void *host, uint64_t bytes, Launch launch) {
+    void *dev = nullptr;
+    int rc = gs_tmp_alloc(c, bytes, &dev);
+    if (rc) return rc;
+    if ((rc = gs_push(c, dev, host, bytes)) == GS_OK) rc = launch((const void *)dev);
+    gs_tmp_free(c, dev);
+    return rc;
+}
+
 // The live parameter handles of both units, each with the serial number it was created under: what outlives a handle and keeps its
-// pointer (a sparse tree, sparse_tree.h) asks here before it dereferences it, so a destroyed hash is an error code and not a read of
+// pointer (a sparse tree, field_tree.h) asks here before it dereferences it, so a destroyed hash is an error code and not a read of
 // freed memory.  One registry per library: a function-local static of an inline function.
 struct sponge_registry {
     std::mutex mutex;

@@ -2,7 +2,7 @@
 // hash units share.  A unit brings its kernel: ONE launch walks every level of every path with the running node in registers, the
 // unit's own permutation inlined into it, so a node computed here is the node its tree build computes.
 //   check     the arguments after the unit's own (its handle, and that two nodes fit its state): depth, count, the arrays, the indexes.
-//   run       the indexes go up through the stream-ordered scratch (gs_tmp_alloc / gs_push) and the unit's launch reads them there.
+//   run       the indexes go up through the stream-ordered scratch (sponge_with_upload) and the unit's launch reads them there.
 // There is no body macro: the two walks have no body in common — hades.hip walks a path per thread, rescue.hip a path per group of lanes.
 // Nothing here is host work beyond the argument check: no plan, no sort, nothing in proportion to the depth.
 #pragma once
@@ -26,12 +26,7 @@ static inline int tree_verify_check(gs_ctx *c, const char *who, uint32_t depth, 
 // count >= 1 and the arguments have passed tree_verify_check.
 template <class Launch>
 static inline int tree_verify_run(gs_ctx *c, const uint64_t *indexes_host, uint64_t count, Launch launch) {
-    void *d_idx = nullptr;
-    int rc = gs_tmp_alloc(c, count * 8, &d_idx);
-    if (rc) return rc;
-    if ((rc = gs_push(c, d_idx, indexes_host, count * 8)) == GS_OK) rc = launch((const uint64_t *)d_idx);
-    gs_tmp_free(c, d_idx);                                                   // (stream-ordered cache: the launch above still reads it)
-    return rc;
+    return sponge_with_upload(c, indexes_host, count * 8, [&](const void *idx) { return launch((const uint64_t *)idx); });
 }
 
 // what a call HAS to move: the paths, the replacing leaves where given, the indexes, the roots

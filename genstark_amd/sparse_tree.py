@@ -1,4 +1,4 @@
-"""Sparse Merkle trees of fixed depth kept on the device (include/gstark_sparse_tree.h, csrc/sparse_tree.h, csrc/sparse_tree_plan.h):
+"""Sparse Merkle trees of fixed depth kept on the device (include/gstark_sparse_tree.h, csrc/field_tree.hip, csrc/sparse_tree_plan.h):
 the producing side for key spaces no dense tree can hold, with the interface of the dense trees of field_tree.py.
 
 A tree of depth d (1 .. 36) IS the dense heap tree of 2^d leaves whose leaves all hold `empty` until they are set: root, paths and update

@@ -1,4 +1,5 @@
-/* gstark_hades.h — Hades permutations (Poseidon hashes) and Poseidon Merkle trees on the device (csrc/hades.hip).
+/* gstark_hades.h — Hades permutations (Poseidon hashes) and Poseidon Merkle trees on the device (csrc/hades.hip;
+ * gs_hades_merkle_paths, which hashes nothing, is in csrc/field_tree.hip).
  *
  * The permutation is the one of the reference's examples/poseidon/utils.ts:19-49 (createHash): the state is the inputs followed by zeros
  * up to `width`; round i < full_rounds + partial_rounds adds round constant row i, raises to `alpha` (every element in a full round:

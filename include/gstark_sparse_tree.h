@@ -1,5 +1,5 @@
 /* gstark_sparse_tree.h — sparse Merkle trees of fixed depth kept on the device, over the node functions of gs_hades_merkle
- * (gstark_hades.h) and gs_rescue_merkle (gstark_rescue.h): csrc/sparse_tree.h, csrc/sparse_tree_plan.h.
+ * (gstark_hades.h) and gs_rescue_merkle (gstark_rescue.h): csrc/field_tree.hip, csrc/sparse_tree_plan.h.
  *
  * A tree of depth d, 1 .. 36, IS the dense heap tree of 2^d leaves of gs_*_merkle whose leaves all hold one `empty` value until they are
  * set: every node, path and update record is bit for bit that tree's.  empties[0] = empty, empties[l + 1] = node(empties[l], empties[l]);

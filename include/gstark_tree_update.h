@@ -1,5 +1,5 @@
 /* gstark_tree_update.h — batches of leaf updates applied to a device-resident Merkle tree of gs_hades_merkle (gstark_hades.h) or
- * gs_rescue_merkle (gstark_rescue.h), with the witness of every update (csrc/tree_update.h, csrc/tree_update_plan.h).
+ * gs_rescue_merkle (gstark_rescue.h), with the witness of every update (csrc/field_tree.hip, csrc/tree_update_plan.h).
  *
  * `nodes` is a tree in the heap layout those entries write: 2n x digest elements, leaves at n .. 2n - 1, root at 1.  Update j sets leaf
  * indexes_host[j] to leaves[j]; the updates are applied in order j = 0, 1, .. count - 1, repeated indexes allowed, a leaf equal to the

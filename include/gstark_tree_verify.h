@@ -1,6 +1,6 @@
 /* gstark_tree_verify.h — the roots that batches of authentication paths imply, for the Merkle trees of gs_hades_merkle (gstark_hades.h)
  * and gs_rescue_merkle (gstark_rescue.h): the consuming side of gs_hades_merkle_paths and of gstark_tree_update.h
- * (csrc/tree_verify.h, the kernels in csrc/hades.hip and csrc/rescue.hip).
+ * (csrc/tree_verify.h; the path walks are kernels of csrc/hades.hip and csrc/rescue.hip, the gather that feeds them one of csrc/field_tree.hip).
  *
  * `paths` is a device array of count x (depth + 1) x digest elements in exactly the layout gs_hades_merkle_paths and the before_out of
  * gs_*_merkle_update write: per path the leaf, then its `depth` siblings bottom-up (digest = 1 for Rescue).  indexes_host[k] < 2^depth is

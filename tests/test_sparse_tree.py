@@ -1,4 +1,4 @@
-"""Sparse Merkle trees of fixed depth on the device: include/gstark_sparse_tree.h, csrc/sparse_tree_plan.h, csrc/sparse_tree.h,
+"""Sparse Merkle trees of fixed depth on the device: include/gstark_sparse_tree.h, csrc/sparse_tree_plan.h, csrc/field_tree.hip,
 genstark_amd/sparse_tree.py, the sparse classes of js/field_tree.js.
 
 The definition is the oracle: a sparse tree of depth d is the dense tree of 2^d leaves that all hold `empty` until set, so for small
@@ -424,6 +424,36 @@ def test_rescue_in_another_flavour_against_the_dense_device_tree():
         with pytest.raises(GstarkError, match='rescue_sparse_create: two nodes do not fit'):
             be.call('gs_rescue_sparse_create', h2.handle(), 9, None, 1, C.byref(tree))
         assert not tree.value
+    finally:
+        be.close()
+
+
+@pytest.mark.gpu
+def test_families_interleaved_on_one_context():
+    """a tree reaches its family's hash through a pointer it carries: calls on a Poseidon sparse tree, a Rescue sparse tree and a dense
+    tree of each family, alternating call by call on one context, give what the same calls give on fresh trees one tree at a time"""
+    be = Backend(device=0, modulus=_abi.MODULUS_64)
+    try:
+        f = PrimeField(backend=be)
+        rng = random.Random(0x1A7E)
+        poseidon, rescue = hades_families(f)[0], Family('rescue', random_rescue(f, rng, 3, 2), 1)
+        depth, indexes = 3, [5, 4, 5, 2]               # a repeat, a sibling pair, a leaf of its own
+        makers = [lambda: poseidon.sparse(depth), lambda: rescue.sparse(depth), lambda: poseidon.dense([0] * 8), lambda: rescue.dense([0] * 8)]
+        new = [[family.leaf(rng) for _ in indexes] for family in (poseidon, rescue)] * 2        # the same leaves for a family's two trees
+
+        def calls(tree, leaves, j):
+            return [tree.update(indexes[j], leaves[j]), tree.root, tree.proveMany(range(8))]
+        alone = []
+        for make, leaves in zip(makers, new):
+            tree = make()
+            alone.append([calls(tree, leaves, j) for j in range(len(indexes))])
+        trees = [make() for make in makers]
+        mixed = [[] for _ in trees]
+        for j in range(len(indexes)):
+            for k, (tree, leaves) in enumerate(zip(trees, new)):
+                mixed[k].append(calls(tree, leaves, j))
+        assert mixed == alone
+        assert mixed[0] == mixed[2] and mixed[1] == mixed[3] and mixed[0] != mixed[1]      # sparse = dense within a family; the families differ
     finally:
         be.close()
 

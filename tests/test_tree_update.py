@@ -1,5 +1,5 @@
 """Batched updates of the device Merkle trees with every update's witness: include/gstark_tree_update.h, csrc/tree_update_plan.h,
-csrc/tree_update.h, FieldMerkleTree.update / updateMany (genstark_amd/field_tree.py), DeviceTree.update / updateMany (js/field_tree.js).
+csrc/field_tree.hip, FieldMerkleTree.update / updateMany (genstark_amd/field_tree.py), DeviceTree.update / updateMany (js/field_tree.js).
 
 Every comparison is equality with host integers.  CPU tier: the header and the binding table, the host plan on its own under the
 sanitizers (tests/host_harness/tree_update_plan_host.cpp), and updateMany on libraries without the entries (the host path) against the
@@ -462,6 +462,64 @@ def test_bad_arguments_are_refused_by_the_library(hip_backend):
         with pytest.raises(GstarkError, match='hades_merkle_update: nodes of'):
             call('gs_hades_merkle_update', h3.handle(), nodes, 4, digest, one, ptr, 1, ptr, ptr)
     assert tree.deviceNodes.toBuffer() == raw         # no refusal and no empty batch has touched the tree
+
+
+# ---- the pin recorded before the family-neutral tree code got a unit of its own (csrc/field_tree.hip) ---------------------------------
+FIELD_TREE_PIN = os.path.join(ROOT, 'tests', 'golden', 'field_tree_traffic.json')
+FIELD_TREE_FLAVOURS = {'p128': None, 'q64': _abi.MODULUS_64}
+
+
+def field_tree_sequence(be):
+    """What tests/golden/make_field_tree_traffic.py records and the test below replays, per family (Poseidon with nodes of one and of two
+    elements, Rescue): a tree of 8 leaves, five updates (leaf 5 and leaf 4 twice each — siblings, so `same` and `pred >= 0` occur — and
+    leaf 2, whose sibling no update touches: `pred < 0`), proveMany of three indexes, pathRoots with and without replacing leaves, and a
+    sparse tree of depth 3 with the same updates and the paths of a set and an unset index.  -> {family: {'traffic': Backend.traffic()
+    over all of it, 'values': everything read back}}, tuples as lists (what JSON gives back)"""
+    from genstark_amd.sparse_tree import HadesSparseMerkleTree, RescueSparseMerkleTree
+    f = PrimeField(backend=be)
+    p, rng = f.modulus, random.Random(0xF1E1D)
+    plain = lambda v: [plain(x) for x in v] if isinstance(v, (list, tuple)) else v
+    out = {}
+    for name, h, digest in (('poseidon1', HadesHash(f, 3, 2, 1, 3), 1), ('poseidon2', HadesHash(f, 3, 2, 1, 6), 2), ('rescue', random_rescue(f, rng, 3, 2), 1)):
+        rescue = isinstance(h, RescueHash)
+        leaf = lambda: rng.randrange(p) if digest == 1 else (rng.randrange(p), rng.randrange(p))
+        leaves, indexes, probe = [leaf() for _ in range(8)], [5, 4, 5, 2, 4], [4, 5, 0]
+        new, replacing = [leaf() for _ in indexes], [leaf() for _ in probe]
+        be.traffic(True)
+        dense = RescueMerkleTree(h, f.newVectorFrom(leaves)) if rescue else HadesMerkleTree(h, leaves, digest)
+        values = {'nodes': dense.nodes[1:]}
+        values['records'] = [[r.before, r.root] for r in dense.updateMany(indexes, new)]
+        values['nodes after'] = dense.nodes[1:]
+        paths = dense.proveMany(probe)
+        values['paths'] = paths
+        values['path roots'] = type(dense).pathRoots(h, probe, paths)
+        values['path roots of other leaves'] = type(dense).pathRoots(h, probe, paths, leaves=replacing)
+        sparse = RescueSparseMerkleTree(h, 3) if rescue else HadesSparseMerkleTree(h, 3, digest)
+        values['sparse empties'] = sparse.empties
+        values['sparse records'] = [[r.before, r.root] for r in sparse.updateMany(indexes, new)]
+        values['sparse root'], values['sparse stored'] = sparse.root, sparse.stored
+        values['sparse paths'] = sparse.proveMany([5, 7])
+        out[name] = {'traffic': be.traffic(), 'values': {key: plain(v) for key, v in values.items()}}
+        be.traffic(False)
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', sorted(FIELD_TREE_FLAVOURS))
+def test_field_tree_matches_the_recorded_parent(name):
+    """every launch (label, count, bytes, units) and every value of field_tree_sequence as the library computed them while the
+    family-neutral kernels and drivers still stood in hades.hip and the two header templates"""
+    with open(FIELD_TREE_PIN) as fh:
+        want = json.load(fh)[name]
+    be = Backend(device=0, modulus=FIELD_TREE_FLAVOURS[name]) if FIELD_TREE_FLAVOURS[name] else Backend(device=0)
+    try:
+        got = field_tree_sequence(be)
+    finally:
+        be.close()
+    assert sorted(got) == sorted(want)
+    for family in want:
+        assert got[family]['traffic'] == want[family]['traffic'], family
+        assert got[family]['values'] == want[family]['values'], family
 
 
 # ---- node ---------------------------------------------------------------------------------------------------------------------------
