@@ -18,6 +18,16 @@ def field_for(backend):
     return PrimeField(backend=backend)
 
 
+def rand_for(backend):
+    """rand_elements of the backend's field: conftest's for the 128-bit field (the same draws as ever), flavour_cases' (edge values
+    of that modulus) for every other build flavour of the library."""
+    q = backend.modulus
+    if q == P:
+        return rand_elements
+    from flavour_cases import rand_elements as flavour_rand
+    return lambda rng, n, edge=0.1: flavour_rand(rng, n, q, edge)
+
+
 def check_pointwise(backend, rng, n):
     f = field_for(backend)
     a, b = rand_elements(rng, n), rand_elements(rng, n)
@@ -37,11 +47,12 @@ def check_pointwise(backend, rng, n):
 
 def check_inverse_with_zeros(backend, rng, n):
     f = field_for(backend)
-    a = rand_elements(rng, n)
+    q = f.modulus
+    a = rand_for(backend)(rng, n)
     for i in range(0, n, 3):
         a[i] = 0
     got = f.invVectorElements(f.newVectorFrom(a)).toValues()
-    assert got == [pow(x, P - 2, P) if x else 0 for x in a]
+    assert got == [pow(x, q - 2, q) if x else 0 for x in a]
     zeros = f.invVectorElements(f.newVectorFrom([0] * n)).toValues()
     assert zeros == [0] * n
 
@@ -133,11 +144,12 @@ def check_fri_fold(backend, rng, logn, depth):
     """gs_fri_fold == transposeVector + interpolateQuarticBatch + evalQuarticBatch (the members it fuses), on layer `depth`."""
     import ctypes as C
     f = field_for(backend)
+    P = f.modulus                                   # (the field of the backend's build flavour; elements of f.elementSize bytes)
     n = 1 << logn
     step = 4 ** depth
     m = n // step
     w = f.getRootOfUnity(n)
-    column = f.newVectorFrom(rand_elements(rng, m))
+    column = f.newVectorFrom(rand_for(backend)(rng, m))
     x = rng.randrange(P)
     out = f.newVector(m // 4)
     f.backend.call('gs_fri_fold', f.le(w), n, step, C.c_void_p(column.ptr), m, f.le(x), C.c_void_p(out.ptr))
@@ -176,6 +188,7 @@ def check_mimc_composition(backend, rng, logn, logsteps, nroots):
     """gs_mimc_composition against its definition on Python integers."""
     import ctypes as C
     f = field_for(backend)
+    P, rand_elements = f.modulus, rand_for(backend)   # (the field of the backend's build flavour)
     n, steps = 1 << logn, 1 << logsteps
     e = n // steps
     w = f.getRootOfUnity(n)
@@ -408,23 +421,21 @@ def merkle_commit_bytes(backend, alg, cols_raw, n, fused=True):
     if fused == 'seed':
         # gs_merkle_commit_rows_seed: the same tree; its last launch posts the root and derives prng(root) (LowDegreeProver.ts:194)
         import hashlib
-        point, ticket = be.alloc(16), C.c_uint64()
+        point, ticket = be.alloc(es), C.c_uint64()
         be.call('gs_merkle_commit_rows_seed', a, arr, len(ptrs), n, C.c_void_p(leaves), C.c_void_p(nodes), C.c_void_p(point), C.byref(ticket))
         root = C.create_string_buffer(32)
         be.call('gs_readback_wait', ticket.value, root)
         assert root.raw == be.download(nodes + 32, 32)
-        if es == 16:
-            from genstark_amd.field import MODULUS
-            assert int.from_bytes(be.download(point, 16), 'little') == int.from_bytes(hashlib.sha256(root.raw).digest(), 'big') % MODULUS
+        assert int.from_bytes(be.download(point, es), 'little') == int.from_bytes(hashlib.sha256(root.raw).digest(), 'big') % be.modulus
         # either half alone
         t2 = C.c_uint64()
         be.call('gs_merkle_commit_rows_seed', a, arr, len(ptrs), n, C.c_void_p(leaves), C.c_void_p(nodes), None, C.byref(t2))
         r2 = C.create_string_buffer(32)
         be.call('gs_readback_wait', t2.value, r2)
         assert r2.raw == root.raw
-        p2 = be.alloc(16)
+        p2 = be.alloc(es)
         be.call('gs_merkle_commit_rows_seed', a, arr, len(ptrs), n, C.c_void_p(leaves), C.c_void_p(nodes), C.c_void_p(p2), None)
-        assert be.download(p2, 16) == be.download(point, 16)
+        assert be.download(p2, es) == be.download(point, es)
         be.free(point); be.free(p2)
     elif fused:
         be.call('gs_merkle_commit_rows', a, arr, len(ptrs), n, C.c_void_p(leaves), C.c_void_p(nodes))
@@ -796,7 +807,7 @@ def check_composition_tail(backend, rng, logn, logsteps, per_row, lcount, adjust
     for cross-backend comparison."""
     be = backend
     f = field_for(be)
-    p = f.modulus
+    p, rand_elements = f.modulus, rand_for(be)      # (the field of the backend's build flavour)
     n, steps = 1 << logn, 1 << logsteps
     e = n // steps
     omega = f.getRootOfUnity(n)

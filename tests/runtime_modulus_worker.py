@@ -1,9 +1,12 @@
-"""tests/runtime_modulus_worker.py <modulus> <oracle|hip|both> — ONE modulus per process (the runtime-modulus libraries fix their field once:
+"""tests/runtime_modulus_worker.py <modulus> <oracle|hip|both> [kernels] — ONE modulus per process (the runtime-modulus libraries fix their field once:
 gs_set_modulus, include/gstark.h).  On each backend asked for: every vector member and the NTT against Python integers
 (test_small_fields.check_arithmetic), then two STARKs over the field — MiMC (x <- x^3 + k, 64 cyclic constants) and a two-register
 degree-5 program AIR — proved by the mirror AND by the native driver's runtime-modulus build (same bytes), verified by the mirror, by
 the native verifier and by the device-free verifier (HostField: Python integers).  `both`: the HIP library's bytes == the oracle's.
-Prints one JSON line {"modulus", "backends", "proofs": [sha256...]}."""
+With `kernels`, each backend also runs the kernel-level checks of tests/flavour_cases.py on this modulus — transforms up to 2^16 points
+(every two-pass plan), batch inversions up to 40 000 elements, leaf hashing and Merkle trees up to 2^9 leaves, the fused FRI /
+composition entries — against Python integers (`both`: on the HIP library; the oracle's bytes must equal them).
+Prints one JSON line {"modulus", "backends", "proofs": [sha256...]} (with `kernels`: and "kernels": {case: digest})."""
 import hashlib
 import json
 import os
@@ -67,17 +70,36 @@ def run(backend, q):
     return out
 
 
+def run_kernels(backend, q, reference):
+    """reference=False: the oracle beside the HIP library, for its bytes alone.  Its plain `%` on 512-bit products makes the five FRI
+    layers over 2^17 values a matter of minutes there, so that one case is left to the HIP library's comparison with Python integers,
+    hashlib and its own member sequence."""
+    import flavour_cases
+    return flavour_cases.run_groups(backend, q % 1000, ntt_max_logn=16, inverse_max_n=40000, merkle_max_logn=9,
+                                    fri_layers_max_logm=17 if reference else 13, reference=reference)
+
+
 if __name__ == '__main__':
     q, which = int(sys.argv[1]), sys.argv[2]
-    results = {}
+    kernels = len(sys.argv) > 3 and sys.argv[3] == 'kernels'
+    results, digests = {}, {}
     if which in ('oracle', 'both'):
-        results['oracle'] = run(Backend(lib_path=os.path.join(ROOT, 'oracle', 'liboracle_rt.so'), allow_test_double=True, modulus=q), q)
+        oracle = Backend(lib_path=os.path.join(ROOT, 'oracle', 'liboracle_rt.so'), allow_test_double=True, modulus=q)
+        results['oracle'] = run(oracle, q)
+        if kernels:                                             # beside the HIP library the oracle only supplies bytes to compare
+            digests['oracle'] = run_kernels(oracle, q, reference=which == 'oracle')
     if which in ('hip', 'both'):
         hip = Backend(device=0, modulus=q)
         assert hip.name == 'hip-gfx950'
         results['hip'] = run(hip, q)
+        if kernels:
+            digests['hip'] = run_kernels(hip, q, reference=True)
     if which == 'both':
         assert results['hip'] == results['oracle'], 'HIP and oracle proofs differ'
+        if kernels:
+            assert set(digests['hip']) - set(digests['oracle']) <= {'fri-layers-17'}
+            differ = sorted(k for k in digests['oracle'] if digests['hip'][k] != digests['oracle'][k])
+            assert not differ, f'HIP and oracle kernel outputs differ: {differ}'
     # one modulus per process: a second one is refused, the same one is accepted again
     lib = os.path.join(ROOT, 'oracle', 'liboracle_rt.so') if which != 'hip' else None
     from genstark_amd._abi import GstarkError
@@ -87,4 +109,7 @@ if __name__ == '__main__':
     except GstarkError as e:
         assert 'ONE modulus per process' in str(e) or 'gs_set_modulus' in str(e), e
     first = next(iter(results.values()))
-    print(json.dumps({'modulus': str(q), 'backends': sorted(results), 'proofs': [hashlib.sha256(d).hexdigest() for d in first]}))
+    rec = {'modulus': str(q), 'backends': sorted(results), 'proofs': [hashlib.sha256(d).hexdigest() for d in first]}
+    if kernels:
+        rec['kernels'] = digests.get('hip') or digests['oracle']
+    print(json.dumps(rec))
