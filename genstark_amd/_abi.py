@@ -209,6 +209,13 @@ _CURVE_SIGNATURES = {
 }
 CURVE_SYMBOLS = tuple(_CURVE_SIGNATURES)
 
+# include/gstark_msm.h: sums of scalar multiples on the same curves; optional in the same way (genstark_amd/curve.py adds on host
+# integers where a library lacks it)
+_MSM_SIGNATURES = {
+    'gs_curve_msm': (_int, [_vp, _bytes, _vp, _vp, _u32, _u32, _u64, _u32, _vp, _vp]),
+}
+MSM_SYMBOLS = tuple(_MSM_SIGNATURES)
+
 # include/gstark_diagnose.h: the scan of the statement diagnosis; optional in the same way (a driver bound to a library without it
 # downloads the matrix and scans it on the host)
 _DIAGNOSE_SIGNATURES = {
@@ -232,7 +239,7 @@ def load_library(path):
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
                               + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_SPARSE_TREE_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
-                              + list(_CURVE_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
+                              + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

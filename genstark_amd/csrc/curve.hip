@@ -14,60 +14,11 @@
 //   output      the addend is one more mixed addition, then ONE inversion (fe_inv: a chain of products like the rest, a tenth of the
 //               multiplication's) gives affine, canonical coordinates; infinity is (0, 0) with its flag set.
 #include "common.h"
+#include "curve_jac.h"                         // jac, fe_select, jac_double, jac_add_affine: shared with msm.hip
 #include "../../include/gstark_curve.h"
 
 #define GS_CURVE_BLOCK 64                      // one wave: a batch of 2^12 multiplications spreads over 64 compute units
 #define GS_CURVE_MAX_COUNT (1ull << 20)
-#define GS_CURVE_DOUBLE_PRODUCTS 10
-#define GS_CURVE_ADD_PRODUCTS 11
-
-struct jac { fe X, Y, Z; };
-
-__device__ __forceinline__ fe fe_select(bool take, const fe &a, const fe &b) {     // take ? a : b, limb by limb: v_cndmask, no branch
-    fe r;
-#pragma unroll
-    for (int i = 0; i < GF_LIMBS; i++) fe_set_limb(r, i, take ? fe_limb(a, i) : fe_limb(b, i));
-    return r;
-}
-__device__ __forceinline__ fe fe_dbl(const fe &a) { return fe_add(a, a); }
-
-// 2 * p for any a (10 products).  Z3 = 2 * Y * Z: infinity stays infinity, a point with Y = 0 becomes infinity.
-__device__ __forceinline__ jac jac_double(const jac &p, const fe &a) {
-    const fe yy = fe_sqr(p.Y), zz = fe_sqr(p.Z);
-    jac r;
-    r.Z = fe_dbl(fe_mul(p.Y, p.Z));
-    const fe s = fe_dbl(fe_dbl(fe_mul(p.X, yy)));                               // 4 X Y^2
-    const fe xx = fe_sqr(p.X);
-    const fe m = fe_add(fe_add(fe_dbl(xx), xx), fe_mul(a, fe_sqr(zz)));         // 3 X^2 + a Z^4
-    r.X = fe_sub(fe_sqr(m), fe_dbl(s));
-    const fe y4 = fe_dbl(fe_dbl(fe_dbl(fe_sqr(yy))));                           // 8 Y^4
-    r.Y = fe_sub(fe_mul(m, fe_sub(s, r.X)), y4);
-    return r;
-}
-
-// p + (x2, y2), the second point affine and finite (11 products).  p infinity: (x2, y2, 1).  Opposite points: H = 0 makes Z3 = 0.
-// Equal points (H = 0 and R = 0, p finite): the doubling of p, by a branch that a scalar multiplication on a curve of cryptographic size
-// never takes.
-__device__ __forceinline__ jac jac_add_affine(const jac &p, const fe &x2, const fe &y2, const fe &a) {
-    const fe zz = fe_sqr(p.Z);
-    const fe h = fe_sub(fe_mul(x2, zz), p.X);
-    const fe r = fe_sub(fe_mul(y2, fe_mul(p.Z, zz)), p.Y);
-    const bool at_infinity = fe_is_zero(p.Z);
-    jac o;
-    if (fe_is_zero(h) && fe_is_zero(r) && !at_infinity) {
-        o = jac_double(p, a);
-    } else {
-        const fe hh = fe_sqr(h);
-        const fe hhh = fe_mul(h, hh), v = fe_mul(p.X, hh);
-        o.Z = fe_mul(p.Z, h);
-        o.X = fe_sub(fe_sub(fe_sqr(r), hhh), fe_dbl(v));
-        o.Y = fe_sub(fe_mul(r, fe_sub(v, o.X)), fe_mul(p.Y, hhh));
-    }
-    o.X = fe_select(at_infinity, x2, o.X);
-    o.Y = fe_select(at_infinity, y2, o.Y);
-    o.Z = fe_select(at_infinity, fe_one(), o.Z);
-    return o;
-}
 
 // out[k] = addends[k] + scalars[k] * points[FIXED ? 0 : k]; 1 <= bits <= 256 (the entry has checked it)
 template <bool FIXED>

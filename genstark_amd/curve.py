@@ -5,13 +5,20 @@ examples/elliptic/pointmul.aa, and the public key x*G, the nonce point k*G and t
 
 A point is a pair (x, y) of integers, the point at infinity is None.  `Curve.mulMany` is ONE launch for the whole batch: one thread per
 multiplication.  On a backend whose library lacks the entry points (the tests' double) the same values come from host integers through
-one complete affine addition (`Curve.add`)."""
+one complete affine addition (`Curve.add`).
+
+`Curve.msm` is the SUM of such products, sum_k scalars[k] * points[k], in one call that reads nothing back (include/gstark_msm.h,
+csrc/msm.hip: the bucket method), `Curve.sumMany` the sum of the points themselves, and `schnorr_verify_batch` the one equation that
+checks a whole block of signatures with one such sum."""
 import ctypes as C
+import secrets as _secrets
 
 from ._abi import MODULUS_224, GstarkError
 from .field import Matrix, Vector
 
-MAX_COUNT = 1 << 20          # multiplications per call (gs_curve_mul)
+MAX_COUNT = 1 << 20          # multiplications per call (gs_curve_mul), terms per sum (gs_curve_msm)
+MAX_WINDOW = 16              # the widest window gs_curve_msm can be forced to
+MAX_BATCH = (1 << 19) - 1    # signatures per schnorr_verify_batch: 2 * count + 1 terms of one sum
 SCALAR_BITS = 256
 
 # the curve of pointmul.aa / lib224.aa with the point the reference's examples multiply (pointMul.ts:23-24, lib224.ts:163: the generator
@@ -66,19 +73,27 @@ class Curve:
         return acc
 
     # ---- device
+    def _has(self, names, header):
+        be = getattr(self.field, 'backend', None)
+        if be is None:
+            return False
+        for name in names:
+            if not hasattr(be.lib, name):
+                if be.name == 'hip-gfx950':
+                    raise GstarkError(f'Curve: the library has no {name} ({header})')
+                return False
+        return True
+
     @property
     def onDevice(self):
         """False on a library without the entry points (the tests' double) and on a HostField: host integers.  A device library that
         lacks only these entries is an error: no quiet host path."""
-        be = getattr(self.field, 'backend', None)
-        if be is None:
-            return False
-        for name in ('gs_curve_mul', 'gs_curve_contains'):
-            if not hasattr(be.lib, name):
-                if be.name == 'hip-gfx950':
-                    raise GstarkError(f'Curve: the library has no {name} (include/gstark_curve.h)')
-                return False
-        return True
+        return self._has(('gs_curve_mul', 'gs_curve_contains'), 'include/gstark_curve.h')
+
+    @property
+    def sumsOnDevice(self):
+        """the same for `msm` and `sumMany` (gs_curve_msm); `mulMany` does not need it"""
+        return self._has(('gs_curve_msm',), 'include/gstark_msm.h')
 
     def _readPoints(self, points, what, count=None):
         """(a device Matrix of rows x 2 | a list of (x, y)), rows"""
@@ -183,6 +198,85 @@ class Curve:
         inf = be.download(flags.ptr, count)
         return [None if inf[k] else (x, y) for k, (x, y) in enumerate(out.toValues())]
 
+    def msm(self, points, scalars, bits=SCALAR_BITS, window=0, device=False):
+        """sum over k of (scalars[k] mod 2^bits) * points[k]: (x, y), or None for infinity.  points: a list of (x, y) / None (an infinite
+        point contributes nothing: it is dropped with its scalar), or a device Matrix of count x 2 finite points; scalars: a list of
+        integers in 0 .. 2^256 - 1, or a device Vector of field elements (each element's bytes are the scalar; bits <= 128 for 16-byte
+        elements).  window: 0 lets the plan choose (csrc/msm_plan.h), 1 .. 16 forces the bucket method with windows of that many bits.
+        With device=True the result is a 1 x 2 Matrix ((0, 0) at infinity) and a Vector of one flag byte (1 = infinity), nothing read
+        back."""
+        f = self.field
+        bits, window = int(bits), int(window)
+        if not 1 <= bits <= SCALAR_BITS:
+            raise GstarkError(f'Curve: {bits} bits of a scalar are outside 1 .. {SCALAR_BITS}')
+        if not 0 <= window <= MAX_WINDOW:
+            raise GstarkError(f'Curve: a window of {window} bits is outside 0 .. {MAX_WINDOW}')
+        stride = 32
+        if isinstance(scalars, Vector):
+            stride, count = scalars.elementSize, scalars.length
+            if stride not in (16, 32):
+                raise GstarkError(f'Curve: scalars are a vector of field elements, not of {stride}-byte entries')
+            if bits > 8 * stride:
+                raise GstarkError(f'Curve: {bits} bits of a scalar, but the elements of the scalar vector have {8 * stride}')
+        else:
+            try:
+                scalars = [int(k) for k in scalars]
+            except (TypeError, ValueError):
+                raise GstarkError('Curve: scalars are integers') from None
+            if any(not 0 <= k < 1 << SCALAR_BITS for k in scalars):
+                raise GstarkError(f'Curve: a scalar is outside 0 .. 2^{SCALAR_BITS} - 1')
+            count = len(scalars)
+        if not isinstance(points, Matrix):
+            points = list(points)
+            if len(points) != count:
+                raise GstarkError(f'Curve: {len(points)} points and {count} scalars: a term is one of each')
+            if any(pt is None for pt in points):
+                if isinstance(scalars, Vector):
+                    scalars, stride = [int(k) for k in scalars.toValues()], 32
+                scalars = [k for k, pt in zip(scalars, points) if pt is not None]
+                points = [pt for pt in points if pt is not None]
+                count = len(points)
+        points, npoints = self._readPoints(points, 'points', count)
+        if npoints != count:
+            raise GstarkError(f'Curve: {npoints} points and {count} scalars: a term is one of each')
+        if count > MAX_COUNT:
+            raise GstarkError(f'Curve: at most 2^20 terms per sum, not {count}')
+        if not self.sumsOnDevice:
+            rows = points.toValues() if isinstance(points, Matrix) else points
+            ks = scalars.toValues() if isinstance(scalars, Vector) else scalars
+            mask, total = (1 << bits) - 1, None
+            for (x, y), k in zip(rows, ks):
+                total = self.add(total, self._hostMul((int(x), int(y)), int(k) & mask))
+            if not device:
+                return total
+            if getattr(f, 'backend', None) is None:
+                raise GstarkError('Curve: device=True needs a field with a backend')
+            flag = Vector(f.backend, 1, element_size=1)
+            f.backend.upload(flag.ptr, bytes([total is None]))
+            return f.newMatrixFrom([list(total or (0, 0))]), flag
+        be = f.backend
+        out, flag = Matrix(be, 1, 2), Vector(be, 1, element_size=1)
+        src = ks = None
+        if count:
+            src = points if isinstance(points, Matrix) else f.newMatrixFrom([list(pt) for pt in points])
+            ks = scalars
+            if not isinstance(scalars, Vector):
+                ks = Vector(be, count * 32, element_size=1)
+                be.upload(ks.ptr, b''.join(k.to_bytes(32, 'little') for k in scalars))
+        be.call('gs_curve_msm', f.le(self.a), C.c_void_p(src.ptr) if count else None, C.c_void_p(ks.ptr) if count else None, stride, bits, count, window,
+                C.c_void_p(out.ptr), C.c_void_p(flag.ptr))
+        if device:
+            return out, flag
+        if be.download(flag.ptr, 1)[0]:
+            return None
+        x, y = out.toValues()[0]
+        return x, y
+
+    def sumMany(self, points, device=False):
+        """the sum of the points (a list of (x, y) / None, or a device Matrix of count x 2): `msm` with every scalar 1 and one bit"""
+        count = points.rowCount if isinstance(points, Matrix) else len(points := list(points))
+        return self.msm(points, [1] * count, bits=1, device=device)
+
     def mul(self, point, scalar):
         """scalar * point"""
         return self.mulMany([tuple(point)], [scalar])[0]
@@ -240,6 +334,31 @@ def schnorr_verify_many(curve, publics, hashes, signatures):
     left = curve.mulMany(curve.G, [s for _, s in signatures])
     right = curve.mulMany([P if ok else curve.G for P, ok in zip(publics, sound)], hashes, addends=[R if ok else None for (R, _), ok in zip(signatures, sound)])
     return [ok and l is not None and l == r for ok, l, r in zip(sound, left, right)]
+
+
+def schnorr_verify_batch(curve, publics, hashes, signatures, rng=None):
+    """ONE bool for the whole batch: True when every signature (R, s) of `hashes[k]` under `publics[k]` satisfies s*G == R + h*P.  A
+    key or an R that is no point of the curve makes the answer False.  Otherwise one random 128-bit z per signature is drawn
+    (`rng.getrandbits` when given, else the `secrets` module) and the batch is accepted exactly when
+        (sum z*s mod n)*G + sum (-z mod n)*R + sum (-z*h mod n)*P
+    is infinity: ONE `Curve.msm` of 2 * count + 1 terms, so at most 2^19 - 1 signatures.
+    The check rests on `curve.order` being the PRIME order of the WHOLE group (true of `curve224`): then every R and P is a multiple of
+    G, and a batch with a wrong signature passes for at most one value of a z in 2^128.  With a cofactor a point of small order could
+    cancel out of the sum.  A False tells nothing about WHICH signature failed: `schnorr_verify_many` does."""
+    _need_base(curve)
+    publics, hashes, signatures = _read_signatures(curve, publics, hashes, signatures, 'schnorr_verify_batch')
+    count = len(publics)
+    if count > MAX_BATCH:
+        raise GstarkError(f'schnorr_verify_batch: at most 2^19 - 1 signatures per batch, not {count}')
+    if not count:
+        return True
+    nonces = [R for R, _ in signatures]
+    if any(len(pt) != 2 for pt in publics + nonces) or not all(curve.containsMany(publics + nonces)):
+        return False
+    n = curve.order
+    zs = [(rng.getrandbits(128) if rng is not None else _secrets.randbits(128)) or 1 for _ in range(count)]
+    scalars = [sum(z * s for z, (_, s) in zip(zs, signatures)) % n] + [-z % n for z in zs] + [-z * h % n for z, h in zip(zs, hashes)]
+    return curve.msm([tuple(curve.G)] + nonces + publics, scalars, bits=n.bit_length()) is None
 
 
 def schnorr_inputs(curve, publics, hashes, signatures):

@@ -3,11 +3,12 @@
 // the device (include/gstark_curve.h through the addon's table): the products, public keys and nonce points that the reference's
 // examples/elliptic/pointMul.ts and the Schnorr example of examples/assembly/lib224.ts assert.  A point is [x, y] (BigInts), the point at
 // infinity is null.  createCurve(field, a, b) has the host members contains / neg / add / mul (BigInt arithmetic, the complete affine
-// law) and the device members mulMany / containsMany: one launch for the whole batch, one thread per multiplication.  A field whose
-// library lacks the entry points (they are optional on an implementation of the ABI) makes the device members throw an Error saying so.
+// law) and the device members mulMany / containsMany: one launch for the whole batch, one thread per multiplication — and msm / sumMany
+// (include/gstark_msm.h): the SUM of the products, or of the points, in one call.  A field whose library lacks the entry points (they
+// are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const { Matrix, Vector } = require('./galois.js');
 
-const MAX_COUNT = 1 << 20, SCALAR_BITS = 256;
+const MAX_COUNT = 1 << 20, SCALAR_BITS = 256, MAX_WINDOW = 16;
 const MODULUS_224 = 2n ** 224n - 2n ** 96n + 1n;
 // the point the reference's examples multiply (pointMul.ts:23-24, lib224.ts:163), b as it follows from it, and the order of the point
 const G_224 = [19277929113566293071110308034699488026831934219452440156649784352033n, 19926808758034470970197974370888749184205991990603949537637343198772n];
@@ -19,6 +20,12 @@ function needDevice(field) {
         if (!field.lib.has || !field.lib.has(symbol)) {
             throw new Error(`the library of the field of ${field.modulus} elements has no ${symbol} entry point (include/gstark_curve.h): curve points are not multiplied on this device library`);
         }
+    }
+}
+
+function needSums(field) {
+    if (!field.lib.has || !field.lib.has('gs_curve_msm')) {
+        throw new Error(`the library of the field of ${field.modulus} elements has no gs_curve_msm entry point (include/gstark_msm.h): curve points are not summed on this device library`);
     }
 }
 
@@ -120,6 +127,42 @@ function createCurve(field, a, b) {
         if (options.device) return { points: out, infinity: flags };
         const inf = flags.toBuffer();
         return out.toValues().map((row, k) => (inf[k] ? null : row));
+    };
+
+    /** the sum over k of (scalars[k] mod 2^bits) * points[k]: [x, y], or null for infinity.  points: an array of [x, y] / null (an
+     *  infinite point contributes nothing: it is dropped with its scalar) or a device Matrix of count x 2 finite points; scalars: BigInts
+     *  in 0 .. 2^256 - 1; bits 1 .. 256 (default 256); window 0 (the plan chooses, default) or 1 .. 16 (the bucket method with windows of
+     *  that many bits). */
+    curve.msm = function (points, scalars, bits = SCALAR_BITS, window = 0) {
+        needSums(field);
+        if (!(bits >= 1 && bits <= SCALAR_BITS)) throw new Error(`${bits} bits of a scalar are outside 1 .. ${SCALAR_BITS}`);
+        if (!(window >= 0 && window <= MAX_WINDOW)) throw new Error(`a window of ${window} bits is outside 0 .. ${MAX_WINDOW}`);
+        scalars = scalars.map(k => BigInt(k));
+        if (scalars.some(k => k < 0n || k >> 256n)) throw new Error(`a scalar is outside 0 .. 2^${SCALAR_BITS} - 1`);
+        const given = points instanceof Matrix ? points.rowCount : points.length;
+        if (given !== scalars.length) throw new Error(`${given} points and ${scalars.length} scalars: a term is one of each`);
+        if (!(points instanceof Matrix)) {
+            scalars = scalars.filter((k, i) => points[i] !== null);
+            points = points.filter(pt => pt !== null);
+        }
+        const count = scalars.length;
+        if (count > MAX_COUNT) throw new Error(`at most 2^20 terms per sum, not ${count}`);
+        const out = new Matrix(field, 1, 2), flag = new Vector(field, 1, undefined, 0n, 1);
+        let src = 0n, keys = 0n;
+        if (count) {
+            src = pointMatrix(points, 'points').ptr;
+            const ks = Buffer.alloc(32 * count);
+            scalars.forEach((k, i) => { for (let w = 0; w < 4; w++) ks.writeBigUInt64LE((k >> BigInt(64 * w)) & 0xffffffffffffffffn, 32 * i + 8 * w); });
+            keys = bytesOnDevice(ks).ptr;
+        }
+        field.lib.call('gs_curve_msm', field.ctx, field.le(a), src, keys, 32, bits, count, window, out.ptr, flag.ptr);
+        return flag.toBuffer()[0] ? null : out.toValues()[0];
+    };
+
+    /** the sum of the points: msm with every scalar 1 and one bit */
+    curve.sumMany = function (points) {
+        const count = points instanceof Matrix ? points.rowCount : points.length;
+        return curve.msm(points, new Array(count).fill(1n), 1, 0);
     };
     return curve;
 }

@@ -148,6 +148,8 @@ const FnDesc kFns[] = {
     // include/gstark_curve.h: OPTIONAL in the same way; `addends` and `addend_inf` may be 0 (every addend / no addend is infinity)
     {"gs_curve_mul", "cbpupippupp"},
     {"gs_curve_contains", "cbbpup"},
+    // include/gstark_msm.h: OPTIONAL in the same way; `points` and `scalars` may be 0 for the empty sum
+    {"gs_curve_msm", "cbppiiuipp"},
     // include/gstark_diagnose.h: OPTIONAL in the same way; the three results are host arrays of `rows` uint64 each (Buffers of 8 * rows bytes)
     {"gs_nonzero_spans", "cpuuuooo"},
     {"gs_pseudorandom_indexes", "biiuio"},
