@@ -216,6 +216,17 @@ _MSM_SIGNATURES = {
 }
 MSM_SYMBOLS = tuple(_MSM_SIGNATURES)
 
+# include/gstark_poly.h: long polynomials at arbitrary points (vanishing polynomial, division, evaluation, interpolation); optional in the
+# same way (genstark_amd/field.py computes on host integers by the quadratic definitions where a library lacks them)
+_POLY_SIGNATURES = {
+    'gs_poly_from_roots': (_int, [_vp, _bytes, _u32, _vp, _u64, _vp]),
+    'gs_poly_div': (_int, [_vp, _bytes, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
+    'gs_poly_eval_points': (_int, [_vp, _bytes, _u32, _vp, _u64, _vp, _u64, _vp]),
+    'gs_poly_interpolate_points': (_int, [_vp, _bytes, _u32, _vp, _vp, _u64, _vp, _vp]),
+    'gs_poly_schoolbook_log2': (_u32, [_u32]),
+}
+POLY_SYMBOLS = tuple(_POLY_SIGNATURES)
+
 # include/gstark_diagnose.h: the scan of the statement diagnosis; optional in the same way (a driver bound to a library without it
 # downloads the matrix and scans it on the host)
 _DIAGNOSE_SIGNATURES = {
@@ -239,7 +250,7 @@ def load_library(path):
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
                               + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_SPARSE_TREE_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
-                              + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
+                              + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_POLY_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

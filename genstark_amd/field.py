@@ -35,6 +35,56 @@ def sha256_bigint(value):
     return int.from_bytes(_sha256(value).digest(), 'big')
 
 
+# ---- the quadratic definitions on host integers: what the members of include/gstark_poly.h compute on a library without the entries
+def _host_mul_linear(poly, x, p):
+    """poly * (X - x)"""
+    out = [0] * (len(poly) + 1)
+    for k, c in enumerate(poly):
+        out[k + 1] = (out[k + 1] + c) % p
+        out[k] = (out[k] - c * x) % p
+    return out
+
+
+def _host_divmod(a, b, p):
+    la, lb = len(a), len(b)
+    if la < lb:
+        return [0], (list(a) + [0] * lb)[:lb - 1]
+    inv, r, q = pow(b[-1], -1, p), list(a), [0] * (la - lb + 1)
+    for k in range(la - lb, -1, -1):
+        q[k] = r[k + lb - 1] * inv % p
+        if q[k]:
+            for j in range(lb):
+                r[k + j] = (r[k + j] - q[k] * b[j]) % p
+    return q, r[:lb - 1]
+
+
+def _host_eval(poly, xs, p):
+    out = []
+    for x in xs:
+        acc = 0
+        for c in reversed(poly):
+            acc = (acc * x + c) % p
+        out.append(acc)
+    return out
+
+
+def _host_interpolate(xs, ys, p):
+    """sum_i y_i / M'(x_i) * M / (X - x_i), M = prod (X - x_i)"""
+    m = [1]
+    for x in xs:
+        m = _host_mul_linear(m, x, p)
+    out = [0] * len(xs)
+    for x, y in zip(xs, ys):
+        q, acc = [0] * len(xs), 0                # M / (X - x) by synthetic division, and its value at x: M'(x)
+        for k in range(len(xs), 0, -1):
+            acc = (m[k] + acc * x) % p
+            q[k - 1] = acc
+        w = y * pow(_host_eval(q, [x], p)[0], -1, p) % p
+        for k, c in enumerate(q):
+            out[k] = (out[k] + w * c) % p
+    return out
+
+
 class _DeviceBuffer:
     """Owns one gs_alloc'd range; freed when the last Vector/Matrix viewing it is collected."""
 
@@ -457,6 +507,132 @@ class PrimeField:
 
     def mulPolyByConstant(self, a, c):
         return self.mulVectorElements(a, c % self.modulus)
+
+    # ---- long polynomials at arbitrary points (include/gstark_poly.h, csrc/poly.hip): n log^2 n field products where
+    # `interpolate` and `evalPolysAtPoints` (both unchanged) take n^2.  Operands are Vectors or lists, results stay on the device.  On a
+    # library without the entries (the tests' double) the same values come from host integers by the quadratic definitions
+    MAX_POLY_LENGTH = 1 << 20
+    # evalPolyAtPoints(method=None) leaves Horner for the tree when coefficients and points both reach this many; None: never.  From
+    # profiles/poly.md (len = points, 128-bit | 224-bit flavour): Horner ahead at 2^14 (0.69 against 2.12 ms | 3.21 against 9.10), the
+    # tree at 2^15 (2.48 against 2.61 | 10.4 against 12.5) and by 3.4 x | 4.1 x at 2^16; other shapes were not measured
+    TREE_EVAL_FROM = 1 << 15
+
+    def _polyEntries(self):
+        """whether the library computes these on the device; a HIP library that lacks only these entries is an error: no quiet host path"""
+        be = self.backend
+        for name in ('gs_poly_from_roots', 'gs_poly_div', 'gs_poly_eval_points', 'gs_poly_interpolate_points'):
+            if not hasattr(be.lib, name):
+                if be.name == 'hip-gfx950':
+                    raise GstarkError(f'PrimeField: the library has no {name} (include/gstark_poly.h)')
+                return False
+        return True
+
+    def _polyOmega(self):
+        """(omega, log2 of its order): getRootOfUnity of the largest power of two that divides p - 1, capped at 2^26; once per field object"""
+        if getattr(self, '_poly_omega', None) is None:
+            log2 = min(((self.modulus - 1) & -(self.modulus - 1)).bit_length() - 1, 26)
+            self._poly_omega = (self.le(self.getRootOfUnity(1 << log2)), log2)
+        return self._poly_omega
+
+    def _polyOperand(self, v, what):
+        """(a device Vector | None, host values | None, length) of a Vector or a list of integers"""
+        if isinstance(v, Vector):
+            n, vec, vals = v.length, v, None
+        else:
+            vals = [int(x) % self.modulus for x in v]
+            n, vec = len(vals), None
+        if n > self.MAX_POLY_LENGTH:
+            raise GstarkError(f'{what}: at most 2^20 elements per operand, not {n}')
+        return vec, vals, n
+
+    def _polyDevice(self, vec, vals):
+        return vec if vec is not None else self.newVectorFrom(vals)
+
+    @staticmethod
+    def _polyHost(vec, vals):
+        return vals if vals is not None else vec.toValues()
+
+    def polyFromRoots(self, xs):
+        """the len(xs) + 1 coefficients of prod (x - xs[i]), low-order first; no root: the polynomial 1"""
+        vec, vals, n = self._polyOperand(xs, 'polyFromRoots')
+        if not self._polyEntries():
+            out = [1]
+            for x in self._polyHost(vec, vals):
+                out = _host_mul_linear(out, x, self.modulus)
+            return self.newVectorFrom(out)
+        omega, log2 = self._polyOmega()
+        out = Vector(self.backend, n + 1)
+        src = self._polyDevice(vec, vals) if n else None
+        self.backend.call('gs_poly_from_roots', omega, log2, C.c_void_p(src.ptr) if n else None, n, C.c_void_p(out.ptr))
+        return out
+
+    def divModPolys(self, a, b):
+        """(q, r) with a = q * b + r: q has len(a) - len(b) + 1 coefficients (one zero when a is shorter than b), r has len(b) - 1 (high
+        zeros included).  The last coefficient of b must not be zero."""
+        avec, avals, la = self._polyOperand(a, 'divModPolys')
+        bvec, bvals, lb = self._polyOperand(b, 'divModPolys')
+        if not la or not lb:
+            raise GstarkError('divModPolys: both polynomials need at least one coefficient')
+        if not self._polyEntries():
+            av, bv = self._polyHost(avec, avals), self._polyHost(bvec, bvals)
+            if not bv[-1]:
+                raise GstarkError('divModPolys: the leading coefficient of b is zero')
+            q, r = _host_divmod(av, bv, self.modulus)
+            return self.newVectorFrom(q), self.newVectorFrom(r)
+        omega, log2 = self._polyOmega()
+        q, r = Vector(self.backend, max(la - lb + 1, 1)), Vector(self.backend, lb - 1)
+        asrc, bsrc = self._polyDevice(avec, avals), self._polyDevice(bvec, bvals)      # (held until the call is enqueued)
+        self.backend.call('gs_poly_div', omega, log2, C.c_void_p(asrc.ptr), la, C.c_void_p(bsrc.ptr), lb, C.c_void_p(q.ptr), C.c_void_p(r.ptr))
+        return q, r
+
+    def divPolys(self, a, b):
+        """galois FiniteField.divPolys: the quotient of divModPolys"""
+        return self.divModPolys(a, b)[0]
+
+    def evalPolyAtPoints(self, poly, xs, method=None):
+        """poly at every x of xs (any points; repeats allowed): a Vector.  method 'horner': gs_eval_polys_at_points, len(poly) * len(xs)
+        products; 'tree': down the subproduct tree of the points (gs_poly_eval_points); None: whichever profiles/poly.md found faster
+        at this size (TREE_EVAL_FROM)."""
+        if method not in (None, 'tree', 'horner'):
+            raise GstarkError(f"evalPolyAtPoints: method {method!r} is not 'tree', 'horner' or None")
+        pvec, pvals, plen = self._polyOperand(poly, 'evalPolyAtPoints')
+        xvec, xvals, n = self._polyOperand(xs, 'evalPolyAtPoints')
+        if method is None:
+            method = 'tree' if self.TREE_EVAL_FROM is not None and min(plen, n) >= self.TREE_EVAL_FROM else 'horner'
+        if method == 'horner':
+            if not n or not plen:
+                return self.newVectorFrom([0] * n)
+            return self.evalPolysAtPoints([self._polyDevice(pvec, pvals)], self._polyHost(xvec, xvals)).row(0)
+        if not self._polyEntries():
+            return self.newVectorFrom(_host_eval(self._polyHost(pvec, pvals), self._polyHost(xvec, xvals), self.modulus))
+        omega, log2 = self._polyOmega()
+        out = Vector(self.backend, n)
+        psrc, xsrc = self._polyDevice(pvec, pvals), self._polyDevice(xvec, xvals)
+        self.backend.call('gs_poly_eval_points', omega, log2, C.c_void_p(psrc.ptr) if plen else None, plen, C.c_void_p(xsrc.ptr) if n else None, n,
+                          C.c_void_p(out.ptr) if n else None)
+        return out
+
+    def interpolateAtPoints(self, xs, ys):
+        """the len(xs) coefficients of the polynomial through (xs[i], ys[i]): any distinct points, any number up to 2^20 (`interpolate`
+        keeps its host route and its cap).  Two equal xs raise."""
+        xvec, xvals, n = self._polyOperand(xs, 'interpolateAtPoints')
+        yvec, yvals, ny = self._polyOperand(ys, 'interpolateAtPoints')
+        if n != ny:
+            raise GstarkError('Number of x coordinates must be the same as number of y coordinates')
+        if not n:
+            raise GstarkError('interpolateAtPoints: at least one point')
+        if not self._polyEntries():
+            xv, yv = self._polyHost(xvec, xvals), self._polyHost(yvec, yvals)
+            if len(set(xv)) != n:
+                raise GstarkError('interpolateAtPoints: two of the x coordinates are equal')
+            return self.newVectorFrom(_host_interpolate(xv, yv, self.modulus))
+        omega, log2 = self._polyOmega()
+        out, flag = Vector(self.backend, n), Vector(self.backend, 1, element_size=1)
+        xsrc, ysrc = self._polyDevice(xvec, xvals), self._polyDevice(yvec, yvals)
+        self.backend.call('gs_poly_interpolate_points', omega, log2, C.c_void_p(xsrc.ptr), C.c_void_p(ysrc.ptr), n, C.c_void_p(out.ptr), C.c_void_p(flag.ptr))
+        if self.backend.download(flag.ptr, 1)[0]:
+            raise GstarkError('interpolateAtPoints: two of the x coordinates are equal')
+        return out
 
     def interpolate(self, xs, ys):
         """BoundaryConstraints.ts:42; LowDegreeProver.ts:243 — Lagrange through a handful of points: O(n^2) host

@@ -228,6 +228,8 @@ class Matrix {
     row(r) { return new Vector(this.field, this.colCount, this.owner, this.offset + BigInt(r * this.colCount * this.elementSize)); }
 }
 
+const TREE_EVAL_FROM = 2 ** 15;     // evalPolyAtPoints(method undefined): the tree from this many coefficients and points (profiles/poly.md)
+
 class PrimeField {
     constructor(modulus, options) {
         const rec = libraryFor(modulus);
@@ -418,6 +420,76 @@ class PrimeField {
     addPolys(a, b) { const n = Math.max(a.length, b.length); return this.addVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     subPolys(a, b) { const n = Math.max(a.length, b.length); return this.subVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     mulPolyByConstant(a, c) { return this.mulVectorElements(a, this.mod(c)); }
+    // ---- long polynomials at arbitrary points (include/gstark_poly.h, csrc/poly.hip; DESIGN 3.16).  Operands are Vectors or arrays of
+    // BigInts, results stay on the device.  A library without the entry points (the tests' double) has no host route here: the members throw
+    _polyNeed(symbol) {
+        if (!this.lib.has || !this.lib.has(symbol)) {
+            throw new Error(`the library of the field of ${this.modulus} elements has no ${symbol} entry point (include/gstark_poly.h): long polynomials are not computed on this device library`);
+        }
+    }
+    /** [omega as bytes, log2 of its order]: a root of unity of the largest power-of-two order dividing p - 1, capped at 2^26; once per field */
+    _polyOmega() {
+        if (!this._polyRoot) {
+            let log2 = 0;
+            while (log2 < 26 && (this.modulus - 1n) % (1n << BigInt(log2 + 1)) === 0n) log2++;
+            this._polyRoot = [this.le(this.getRootOfUnity(2 ** log2)), log2];
+        }
+        return this._polyRoot;
+    }
+    _polyOperand(v, what) {
+        if (!(v instanceof Vector)) v = this.newVectorFrom(Array.from(v, x => BigInt(x)));
+        this._own(v);
+        if (v.length > 2 ** 20) throw new Error(`${what}: at most 2^20 elements per operand, not ${v.length}`);
+        return v;
+    }
+    /** the xs.length + 1 coefficients of the product of (x - xs[i]), low-order first */
+    polyFromRoots(xs) {
+        this._polyNeed('gs_poly_from_roots');
+        xs = this._polyOperand(xs, 'polyFromRoots');
+        const [omega, log2] = this._polyOmega(), out = new Vector(this, xs.length + 1);
+        this.lib.call('gs_poly_from_roots', this.ctx, omega, log2, xs.length ? xs.ptr : 0n, xs.length, out.ptr);
+        return out;
+    }
+    /** [q, r] with a = q * b + r: q of a.length - b.length + 1 coefficients (one zero when a is shorter), r of b.length - 1 */
+    divModPolys(a, b) {
+        this._polyNeed('gs_poly_div');
+        a = this._polyOperand(a, 'divModPolys'); b = this._polyOperand(b, 'divModPolys');
+        if (!a.length || !b.length) throw new Error('divModPolys: both polynomials need at least one coefficient');
+        const [omega, log2] = this._polyOmega();
+        const q = new Vector(this, Math.max(a.length - b.length + 1, 1)), r = new Vector(this, b.length - 1);
+        this.lib.call('gs_poly_div', this.ctx, omega, log2, a.ptr, a.length, b.ptr, b.length, q.ptr, r.ptr);
+        return [q, r];
+    }
+    divPolys(a, b) { return this.divModPolys(a, b)[0]; }
+    /** poly at every x of xs: method 'tree' (gs_poly_eval_points), 'horner' (gs_eval_polys_at_points) or undefined: the tree from 2^15
+     *  coefficients and points on (profiles/poly.md: Horner is ahead at 2^14, the tree at 2^15), Horner below */
+    evalPolyAtPoints(poly, xs, method) {
+        if (method !== undefined && method !== 'tree' && method !== 'horner') throw new Error(`evalPolyAtPoints: method ${method} is not 'tree' or 'horner'`);
+        poly = this._polyOperand(poly, 'evalPolyAtPoints');
+        if (method === undefined) method = Math.min(poly.length, xs.length) >= TREE_EVAL_FROM ? 'tree' : 'horner';
+        if (method !== 'tree') {
+            const points = xs instanceof Vector ? xs.toValues() : Array.from(xs, x => this.mod(BigInt(x)));
+            const out = new Vector(this, points.length);
+            if (points.length) this.lib.call('gs_eval_polys_at_points', this.ctx, poly.ptr, 1, poly.length, [poly.length], this.packLe(points, x => x), points.length, out.ptr);
+            return out;
+        }
+        this._polyNeed('gs_poly_eval_points');
+        xs = this._polyOperand(xs, 'evalPolyAtPoints');
+        const [omega, log2] = this._polyOmega(), out = new Vector(this, xs.length);
+        this.lib.call('gs_poly_eval_points', this.ctx, omega, log2, poly.length ? poly.ptr : 0n, poly.length, xs.length ? xs.ptr : 0n, xs.length, xs.length ? out.ptr : 0n);
+        return out;
+    }
+    /** the coefficients of the polynomial through (xs[i], ys[i]): any distinct points, up to 2^20 of them; equal points throw */
+    interpolateAtPoints(xs, ys) {
+        this._polyNeed('gs_poly_interpolate_points');
+        xs = this._polyOperand(xs, 'interpolateAtPoints'); ys = this._polyOperand(ys, 'interpolateAtPoints');
+        if (xs.length !== ys.length) throw new Error('Number of x coordinates must be the same as number of y coordinates');
+        if (!xs.length) throw new Error('interpolateAtPoints: at least one point');
+        const [omega, log2] = this._polyOmega(), out = new Vector(this, xs.length), flag = new Vector(this, 1, undefined, 0n, 1);
+        this.lib.call('gs_poly_interpolate_points', this.ctx, omega, log2, xs.ptr, ys.ptr, xs.length, out.ptr, flag.ptr);
+        if (flag.toBuffer()[0]) throw new Error('interpolateAtPoints: two of the x coordinates are equal');
+        return out;
+    }
     /** a square root of g (g of order `order`, a power of two): an element of order 2 * order, found in the field's 2-power subgroup bit by bit */
     _rootAbove(g, order) {
         const w = this.getRootOfUnity(2 * order), g0 = this.mul(w, w);

@@ -150,6 +150,11 @@ const FnDesc kFns[] = {
     {"gs_curve_contains", "cbbpup"},
     // include/gstark_msm.h: OPTIONAL in the same way; `points` and `scalars` may be 0 for the empty sum
     {"gs_curve_msm", "cbppiiuipp"},
+    // include/gstark_poly.h: OPTIONAL in the same way; an operand of no element may be 0
+    {"gs_poly_from_roots", "cbipup"},
+    {"gs_poly_div", "cbipupupp"},
+    {"gs_poly_eval_points", "cbipupup"},
+    {"gs_poly_interpolate_points", "cbippupp"},
     // include/gstark_diagnose.h: OPTIONAL in the same way; the three results are host arrays of `rows` uint64 each (Buffers of 8 * rows bytes)
     {"gs_nonzero_spans", "cpuuuooo"},
     {"gs_pseudorandom_indexes", "biiuio"},
