@@ -227,6 +227,16 @@ _POLY_SIGNATURES = {
 }
 POLY_SYMBOLS = tuple(_POLY_SIGNATURES)
 
+# include/gstark_sqrt.h: square roots in the field, the lift of x coordinates to curve points and its inverse; optional in the same way
+# (genstark_amd/field.py and genstark_amd/curve.py compute on host integers where a library lacks them)
+_SQRT_SIGNATURES = {
+    'gs_field_sqrt': (_int, [_vp, _vp, _u64, _vp, _vp]),
+    'gs_curve_lift_x': (_int, [_vp, _bytes, _bytes, _vp, _vp, _u64, _vp, _vp]),
+    'gs_curve_compress': (_int, [_vp, _vp, _u64, _vp, _vp]),
+    'gs_field_sqrt_plan': (_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+}
+SQRT_SYMBOLS = tuple(_SQRT_SIGNATURES)
+
 # include/gstark_diagnose.h: the scan of the statement diagnosis; optional in the same way (a driver bound to a library without it
 # downloads the matrix and scans it on the host)
 _DIAGNOSE_SIGNATURES = {
@@ -250,7 +260,8 @@ def load_library(path):
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
                               + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_SPARSE_TREE_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
-                              + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_POLY_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
+                              + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_POLY_SIGNATURES.items()) + list(_SQRT_SIGNATURES.items())
+                              + list(_DIAGNOSE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

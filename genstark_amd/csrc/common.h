@@ -122,6 +122,8 @@ struct gs_ctx {
     int up_half = 0;
     hipEvent_t up_done[2] = {};
     bool up_pending[2] = {false, false};
+    // the plan and the device tables of square roots in this field (sqrt.hip): built by the first call that takes one, freed by gs_sqrt_destroy
+    void *sqrt_state = nullptr;
 };
 
 int gs_fail(gs_ctx *c, int code, const char *fmt, ...);
@@ -209,6 +211,8 @@ int gs_jit_trace_segments(gs_ctx *c, const AirProgram &p, const AirProgram &init
                           const fe *drows, uint64_t segments, uint64_t seglen, fe *out);
 int gs_jit_constraints(gs_ctx *c, const AirProgram &p, const fe *dconst, const fe *columns, uint64_t nc, uint64_t shift, const fe *statics, fe *out,
                        uint64_t prow, uint64_t pstride);
+
+void gs_sqrt_destroy(gs_ctx *c);                 // sqrt.hip: the context's square-root tables, if it built any
 
 // NTT entry points implemented in ntt.hip and used by other units
 void gs_plans_destroy(gs_ctx *c);

@@ -124,6 +124,7 @@ void gs_ctx_destroy(gs_ctx *c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     gs_plans_destroy(c);
+    gs_sqrt_destroy(c);
     for (auto &kv : c->free_blocks) hipFree(kv.second);
     for (auto &kv : c->live_blocks) hipFree(kv.first);
     if (c->h_stage) hipHostFree(c->h_stage);

@@ -14,7 +14,7 @@ import ctypes as C
 import secrets as _secrets
 
 from ._abi import MODULUS_224, GstarkError
-from .field import Matrix, Vector
+from .field import Matrix, Vector, host_sqrt
 
 MAX_COUNT = 1 << 20          # multiplications per call (gs_curve_mul), terms per sum (gs_curve_msm)
 MAX_WINDOW = 16              # the widest window gs_curve_msm can be forced to
@@ -280,6 +280,120 @@ class Curve:
     def mul(self, point, scalar):
         """scalar * point"""
         return self.mulMany([tuple(point)], [scalar])[0]
+
+    # ---- compressed points (include/gstark_sqrt.h, csrc/sqrt.hip): x and the parity y & 1
+    @property
+    def liftsOnDevice(self):
+        """the same for `liftX`, `compressMany` and `decompressMany` (gs_curve_lift_x, gs_curve_compress)"""
+        return self._has(('gs_field_sqrt', 'gs_curve_lift_x', 'gs_curve_compress', 'gs_field_sqrt_plan'), 'include/gstark_sqrt.h')
+
+    def compress(self, point):
+        """(x, y & 1) of a finite point"""
+        x, y = point
+        return int(x), int(y) & 1
+
+    def decompress(self, x, parity):
+        """the point (x, y) with y & 1 == parity, or None where x^3 + a*x + b is not a square; y = 0 answers both parities"""
+        p = self.field.modulus
+        x = int(x)
+        if not 0 <= x < p:
+            raise GstarkError('Curve: x is not a canonical element')
+        y = host_sqrt(((x * x + self.a) * x + self.b) % p, p)
+        if y is None:
+            return None
+        return x, (p - y if (int(parity) & 1) and y else y)
+
+    def _deviceFlags(self, flags):
+        out = Vector(self.field.backend, len(flags), element_size=1)
+        if flags:
+            self.field.backend.upload(out.ptr, bytes(flags))
+        return out
+
+    def liftX(self, xs, parities=None, device=False):
+        """the point (x, y) with y & 1 == parities[k] for every x of a list or a device Vector, None where there is none.  parities: None
+        (every y even), a list of 0 / 1, or a device Vector of bytes.  Returns a list of (x, y) / None; with device=True the count x 2
+        Matrix of coordinates ((0, 0) where there is no point) and the Vector of count flag bytes (1 = a point), nothing read back."""
+        f = self.field
+        if isinstance(xs, Vector):
+            if xs.elementSize != f.elementSize:
+                raise GstarkError(f'Curve: xs are a vector of field elements, not of {xs.elementSize}-byte entries')
+            count = xs.length
+        else:
+            try:
+                xs = [int(x) for x in xs]
+            except (TypeError, ValueError):
+                raise GstarkError('Curve: xs are integers') from None
+            if any(not 0 <= x < f.modulus for x in xs):
+                raise GstarkError('Curve: an x is not a canonical element')
+            count = len(xs)
+        if isinstance(parities, Vector):
+            if parities.elementSize != 1:
+                raise GstarkError(f'Curve: parities are a vector of bytes, not of {parities.elementSize}-byte entries')
+            nparities = parities.length
+        elif parities is not None:
+            try:
+                parities = [int(b) for b in parities]
+            except (TypeError, ValueError):
+                raise GstarkError('Curve: parities are 0 or 1') from None
+            if any(b not in (0, 1) for b in parities):
+                raise GstarkError('Curve: parities are 0 or 1')
+            nparities = len(parities)
+        if parities is not None and nparities != count:
+            raise GstarkError(f'Curve: {nparities} parities and {count} xs: one parity each')
+        if count > MAX_COUNT:
+            raise GstarkError(f'Curve: at most 2^20 points per call, not {count}')
+        if not self.liftsOnDevice:
+            xv = xs.toValues() if isinstance(xs, Vector) else xs
+            pv = [0] * count if parities is None else (parities.toValues() if isinstance(parities, Vector) else parities)
+            out = [self.decompress(x, b) for x, b in zip(xv, pv)]
+            if not device:
+                return out
+            if getattr(f, 'backend', None) is None:
+                raise GstarkError('Curve: device=True needs a field with a backend')
+            return (f.newMatrixFrom([list(pt or (0, 0)) for pt in out]) if count else Matrix(f.backend, 0, 2)), self._deviceFlags([pt is not None for pt in out])
+        be = f.backend
+        out, flags = Matrix(be, count, 2), Vector(be, count, element_size=1)
+        if count:
+            src = xs if isinstance(xs, Vector) else f.newVectorFrom(xs)
+            par = parities if isinstance(parities, Vector) or parities is None else self._deviceFlags(parities)
+            be.call('gs_curve_lift_x', f.le(self.a), f.le(self.b), C.c_void_p(src.ptr), C.c_void_p(par.ptr) if par is not None else None, count,
+                    C.c_void_p(out.ptr), C.c_void_p(flags.ptr))
+        if device:
+            return out, flags
+        if not count:
+            return []
+        ok = be.download(flags.ptr, count)
+        return [(x, y) if ok[k] else None for k, (x, y) in enumerate(out.toValues())]
+
+    def decompressMany(self, xs, parities, device=False):
+        """`liftX` with the parities required"""
+        if parities is None:
+            raise GstarkError('Curve: decompressMany needs the parities')
+        return self.liftX(xs, parities, device=device)
+
+    def compressMany(self, points, device=False):
+        """(xs, parities) of finite points (a list of (x, y), or a device Matrix of count x 2): two lists; with device=True a Vector of
+        elements and a Vector of bytes, nothing read back"""
+        f = self.field
+        points, count = self._readPoints(points, 'points', 0)
+        if count > MAX_COUNT:
+            raise GstarkError(f'Curve: at most 2^20 points per call, not {count}')
+        if not self.liftsOnDevice:
+            rows = points.toValues() if isinstance(points, Matrix) else points
+            pairs = [self.compress(pt) for pt in rows]
+            if not device:
+                return [x for x, _ in pairs], [b for _, b in pairs]
+            if getattr(f, 'backend', None) is None:
+                raise GstarkError('Curve: device=True needs a field with a backend')
+            return f.newVectorFrom([x for x, _ in pairs]), self._deviceFlags([b for _, b in pairs])
+        be = f.backend
+        xs, parities = Vector(be, count), Vector(be, count, element_size=1)
+        if count:
+            src = points if isinstance(points, Matrix) else f.newMatrixFrom([list(pt) for pt in points])
+            be.call('gs_curve_compress', C.c_void_p(src.ptr), count, C.c_void_p(xs.ptr), C.c_void_p(parities.ptr))
+        if device:
+            return xs, parities
+        return (xs.toValues(), list(be.download(parities.ptr, count))) if count else ([], [])
 
 
 def curve224(field):

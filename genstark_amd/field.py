@@ -85,6 +85,42 @@ def _host_interpolate(xs, ys, p):
     return out
 
 
+_SQRT_SPLITS = {}
+
+
+def host_two_adicity(p):
+    """s of p - 1 = 2^s * t, t odd"""
+    return ((p - 1) & -(p - 1)).bit_length() - 1
+
+
+def host_sqrt(a, p):
+    """The even one of the two square roots of a modulo the prime p, or None (Tonelli-Shanks on host integers: the answer of
+    gs_field_sqrt, include/gstark_sqrt.h, where a library lacks it; 0 is a square with root 0)."""
+    a %= p
+    if a == 0:
+        return 0
+    if pow(a, (p - 1) // 2, p) != 1:
+        return None
+    if p not in _SQRT_SPLITS:
+        s = host_two_adicity(p)
+        z = next((z for z in range(2, 1000) if pow(z, (p - 1) // 2, p) == p - 1), None)
+        if z is None:
+            raise GstarkError(f'sqrt: modulus is not prime ({p})')
+        _SQRT_SPLITS[p] = (s, (p - 1) >> s, pow(z, (p - 1) >> s, p))
+    s, t, c = _SQRT_SPLITS[p]
+    r, b, m = pow(a, (t + 1) // 2, p), pow(a, t, p), s
+    while b != 1:
+        i, sq = 0, b
+        while sq != 1:
+            sq, i = sq * sq % p, i + 1
+            if i == m:
+                raise GstarkError(f'sqrt: modulus is not prime ({p})')
+        f = pow(c, 1 << (m - i - 1), p)
+        r, c = r * f % p, f * f % p
+        b, m = b * c % p, i
+    return r if r % 2 == 0 else p - r
+
+
 class _DeviceBuffer:
     """Owns one gs_alloc'd range; freed when the last Vector/Matrix viewing it is collected."""
 
@@ -229,6 +265,84 @@ class PrimeField:
             if pow(g, order, self.modulus) == 1 and (order == 1 or pow(g, order // 2, self.modulus) != 1):
                 return g
         raise GstarkError(f'Root of unity for order {order} was not found')
+
+    # ---- square roots (include/gstark_sqrt.h, csrc/sqrt.hip)
+    MAX_SQRT_COUNT = 1 << 20
+
+    def sqrt(self, a):
+        """the even square root of a (as a canonical integer; the other one is p - root), or None for a non-residue"""
+        return host_sqrt(int(a), self.modulus)
+
+    @property
+    def twoAdicity(self):
+        """s of p - 1 = 2^s * t with t odd"""
+        return host_two_adicity(self.modulus)
+
+    def _sqrtEntries(self, who='PrimeField'):
+        """whether the library takes roots on the device; a HIP library that lacks only these entries is an error: no quiet host path"""
+        be = self.backend
+        for name in ('gs_field_sqrt', 'gs_curve_lift_x', 'gs_curve_compress', 'gs_field_sqrt_plan'):
+            if not hasattr(be.lib, name):
+                if be.name == 'hip-gfx950':
+                    raise GstarkError(f'{who}: the library has no {name} (include/gstark_sqrt.h)')
+                return False
+        return True
+
+    def sqrtPlan(self):
+        """gs_field_sqrt_plan: {'twoAdicity', 'windowBits', 'windows', 'productsPerRoot'} of the library's schedule, or None where it has none"""
+        if not self._sqrtEntries():
+            return None
+        vals = [C.c_uint32() for _ in range(4)]
+        self.backend.call('gs_field_sqrt_plan', *[C.byref(v) for v in vals])
+        return dict(zip(('twoAdicity', 'windowBits', 'windows', 'productsPerRoot'), (v.value for v in vals)))
+
+    def _sqrtOperand(self, v, what):
+        if isinstance(v, Vector):
+            if v.elementSize != self.elementSize:
+                raise GstarkError(f'{what}: a vector of field elements, not of {v.elementSize}-byte entries')
+            n, vec, vals = v.length, v, None
+        else:
+            try:
+                vals = [int(x) for x in v]
+            except (TypeError, ValueError):
+                raise GstarkError(f'{what}: the values are integers') from None
+            if any(not 0 <= x < self.modulus for x in vals):
+                raise GstarkError(f'{what}: a value is not a canonical element')
+            n, vec = len(vals), None
+        if n > self.MAX_SQRT_COUNT:
+            raise GstarkError(f'{what}: at most 2^20 elements per call, not {n}')
+        return vec, vals, n
+
+    def _flagVector(self, flags):
+        out = Vector(self.backend, len(flags), element_size=1)
+        if flags:
+            self.backend.upload(out.ptr, bytes(flags))
+        return out
+
+    def sqrtVectorElements(self, v):
+        """(roots, flags) of a Vector or a list of elements: a Vector of the even roots (0 where there is none) and a Vector of one-byte
+        flags (1 = a square, 0 included); one launch, nothing read back"""
+        vec, vals, n = self._sqrtOperand(v, 'sqrtVectorElements')
+        if not self._sqrtEntries():
+            roots = [host_sqrt(x, self.modulus) for x in (vals if vals is not None else vec.toValues())]
+            return self.newVectorFrom([r or 0 for r in roots]), self._flagVector([r is not None for r in roots])
+        roots, flags = Vector(self.backend, n), Vector(self.backend, n, element_size=1)
+        if n:
+            src = vec if vec is not None else self.newVectorFrom(vals)
+            self.backend.call('gs_field_sqrt', C.c_void_p(src.ptr), n, C.c_void_p(roots.ptr), C.c_void_p(flags.ptr))
+        return roots, flags
+
+    def isSquareVectorElements(self, v):
+        """the flags alone (Euler's criterion: one exponentiation, no table)"""
+        vec, vals, n = self._sqrtOperand(v, 'isSquareVectorElements')
+        if not self._sqrtEntries():
+            p = self.modulus
+            return self._flagVector([x == 0 or pow(x, (p - 1) // 2, p) == 1 for x in (vals if vals is not None else vec.toValues())])
+        flags = Vector(self.backend, n, element_size=1)
+        if n:
+            src = vec if vec is not None else self.newVectorFrom(vals)
+            self.backend.call('gs_field_sqrt', C.c_void_p(src.ptr), n, None, C.c_void_p(flags.ptr))
+        return flags
 
     # ---- construction
     def newVector(self, length):

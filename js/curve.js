@@ -5,7 +5,8 @@
 // infinity is null.  createCurve(field, a, b) has the host members contains / neg / add / mul (BigInt arithmetic, the complete affine
 // law) and the device members mulMany / containsMany: one launch for the whole batch, one thread per multiplication — and msm / sumMany
 // (include/gstark_msm.h): the SUM of the products, or of the points, in one call.  A field whose library lacks the entry points (they
-// are optional on an implementation of the ABI) makes the device members throw an Error saying so.
+// are optional on an implementation of the ABI) makes the device members throw an Error saying so.  liftX / decompressMany /
+// compressMany (include/gstark_sqrt.h) go between full points and x with a parity bit, one launch each.
 const { Matrix, Vector } = require('./galois.js');
 
 const MAX_COUNT = 1 << 20, SCALAR_BITS = 256, MAX_WINDOW = 16;
@@ -26,6 +27,14 @@ function needDevice(field) {
 function needSums(field) {
     if (!field.lib.has || !field.lib.has('gs_curve_msm')) {
         throw new Error(`the library of the field of ${field.modulus} elements has no gs_curve_msm entry point (include/gstark_msm.h): curve points are not summed on this device library`);
+    }
+}
+
+function needLifts(field) {
+    for (const symbol of ['gs_curve_lift_x', 'gs_curve_compress']) {
+        if (!field.lib.has || !field.lib.has(symbol)) {
+            throw new Error(`the library of the field of ${field.modulus} elements has no ${symbol} entry point (include/gstark_sqrt.h): curve points are not lifted on this device library`);
+        }
     }
 }
 
@@ -163,6 +172,54 @@ function createCurve(field, a, b) {
     curve.sumMany = function (points) {
         const count = points instanceof Matrix ? points.rowCount : points.length;
         return curve.msm(points, new Array(count).fill(1n), 1, 0);
+    };
+
+    // ---- compressed points (include/gstark_sqrt.h): x and the parity y & 1
+    /** [x, y] with y & 1 == parities[k] for every x of an array of BigInts or a device Vector, null where x^3 + a*x + b is not a square
+     *  (y = 0 answers both parities).  parities: undefined (every y even), an array of 0 / 1, or a device Vector of bytes.
+     *  options.device: { points: Matrix of count x 2 ((0, 0) where there is no point), flags: Vector of count bytes }, nothing read back. */
+    curve.liftX = function (xs, parities, options = {}) {
+        needLifts(field);
+        if (!(xs instanceof Vector)) {
+            xs = Array.from(xs, x => BigInt(x));
+            if (xs.some(x => x < 0n || x >= p)) throw new Error('an x is not a canonical element');
+            xs = field.newVectorFrom(xs);
+        }
+        field._own(xs);
+        if (xs.elementSize !== field.elementSize) throw new Error(`xs are a vector of field elements, not of ${xs.elementSize}-byte entries`);
+        const count = xs.length;
+        if (parities !== undefined && parities !== null && !(parities instanceof Vector)) {
+            parities = Array.from(parities, b => Number(b));
+            if (parities.some(b => b !== 0 && b !== 1)) throw new Error('parities are 0 or 1');
+            parities = bytesOnDevice(Buffer.from(parities));
+        }
+        if (parities) {
+            field._own(parities);
+            if (parities.elementSize !== 1) throw new Error(`parities are a vector of bytes, not of ${parities.elementSize}-byte entries`);
+            if (parities.length !== count) throw new Error(`${parities.length} parities and ${count} xs: one parity each`);
+        }
+        if (count > MAX_COUNT) throw new Error(`at most 2^20 points per call, not ${count}`);
+        const out = new Matrix(field, count, 2), flags = new Vector(field, count, undefined, 0n, 1);
+        if (count) field.lib.call('gs_curve_lift_x', field.ctx, field.le(a), field.le(b), xs.ptr, parities ? parities.ptr : 0n, count, out.ptr, flags.ptr);
+        if (options.device) return { points: out, flags };
+        const ok = flags.toBuffer();
+        return out.toValues().map((row, k) => (ok[k] ? row : null));
+    };
+    /** liftX with the parities required */
+    curve.decompressMany = function (xs, parities, options = {}) {
+        if (parities === undefined || parities === null) throw new Error('decompressMany needs the parities');
+        return curve.liftX(xs, parities, options);
+    };
+    /** { xs, parities } of finite points (an array of [x, y] or a device Matrix of count x 2): an array of BigInts and an array of 0 / 1;
+     *  options.device: a Vector of elements and a Vector of bytes, nothing read back */
+    curve.compressMany = function (points, options = {}) {
+        needLifts(field);
+        const src = pointMatrix(points, 'points'), count = src.rowCount;
+        if (count > MAX_COUNT) throw new Error(`at most 2^20 points per call, not ${count}`);
+        const xs = new Vector(field, count), parities = new Vector(field, count, undefined, 0n, 1);
+        if (count) field.lib.call('gs_curve_compress', field.ctx, src.ptr, count, xs.ptr, parities.ptr);
+        if (options.device) return { xs, parities };
+        return { xs: xs.toValues(), parities: Array.from(parities.toBuffer()) };
     };
     return curve;
 }

@@ -420,6 +420,63 @@ class PrimeField {
     addPolys(a, b) { const n = Math.max(a.length, b.length); return this.addVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     subPolys(a, b) { const n = Math.max(a.length, b.length); return this.subVectorElements(this.padPoly(a, n), this.padPoly(b, n)); }
     mulPolyByConstant(a, c) { return this.mulVectorElements(a, this.mod(c)); }
+    // ---- square roots (include/gstark_sqrt.h, csrc/sqrt.hip).  sqrt is host BigInt arithmetic (Tonelli-Shanks); the vector members are one
+    // launch each and throw on a library without the entry points (the tests' double)
+    _sqrtNeed(symbol) {
+        if (!this.lib.has || !this.lib.has(symbol)) {
+            throw new Error(`the library of the field of ${this.modulus} elements has no ${symbol} entry point (include/gstark_sqrt.h): square roots are not taken on this device library`);
+        }
+    }
+    /** the even square root of a (the other one is p - root), or null for a non-residue */
+    sqrt(a) {
+        const p = this.modulus;
+        a = this.mod(BigInt(a));
+        if (a === 0n) return 0n;
+        if (this.exp(a, (p - 1n) / 2n) !== 1n) return null;
+        if (!this._sqrtSplit) {
+            let s = 0n, t = p - 1n, z = 2n;
+            while (t % 2n === 0n) { t /= 2n; s++; }
+            while (z < 1000n && this.exp(z, (p - 1n) / 2n) !== p - 1n) z++;
+            if (z === 1000n) throw new Error(`sqrt: modulus is not prime (${p})`);
+            this._sqrtSplit = [s, t, this.exp(z, t)];
+        }
+        let [m, t, c] = this._sqrtSplit;
+        let r = this.exp(a, (t + 1n) / 2n), b = this.exp(a, t);
+        while (b !== 1n) {
+            let i = 0n, sq = b;
+            while (sq !== 1n) { sq = sq * sq % p; i++; if (i === m) throw new Error(`sqrt: modulus is not prime (${p})`); }
+            const f = this.exp(c, 1n << (m - i - 1n));
+            r = r * f % p; c = f * f % p; b = b * c % p; m = i;
+        }
+        return r % 2n === 0n ? r : p - r;
+    }
+    _sqrtOperand(v, what) {
+        if (!(v instanceof Vector)) {
+            const vals = Array.from(v, x => BigInt(x));
+            if (vals.some(x => x < 0n || x >= this.modulus)) throw new Error(`${what}: a value is not a canonical element`);
+            v = this.newVectorFrom(vals);
+        }
+        this._own(v);
+        if (v.elementSize !== this.elementSize) throw new Error(`${what}: a vector of field elements, not of ${v.elementSize}-byte entries`);
+        if (v.length > 2 ** 20) throw new Error(`${what}: at most 2^20 elements per call, not ${v.length}`);
+        return v;
+    }
+    /** { roots: Vector of the even roots (0 where there is none), flags: Vector of bytes (1 = a square, 0 included) }, nothing read back */
+    sqrtVectorElements(v) {
+        this._sqrtNeed('gs_field_sqrt');
+        v = this._sqrtOperand(v, 'sqrtVectorElements');
+        const roots = new Vector(this, v.length), flags = new Vector(this, v.length, undefined, 0n, 1);
+        if (v.length) this.lib.call('gs_field_sqrt', this.ctx, v.ptr, v.length, roots.ptr, flags.ptr);
+        return { roots, flags };
+    }
+    /** the flags alone: Euler's criterion */
+    isSquareVectorElements(v) {
+        this._sqrtNeed('gs_field_sqrt');
+        v = this._sqrtOperand(v, 'isSquareVectorElements');
+        const flags = new Vector(this, v.length, undefined, 0n, 1);
+        if (v.length) this.lib.call('gs_field_sqrt', this.ctx, v.ptr, v.length, 0n, flags.ptr);
+        return flags;
+    }
     // ---- long polynomials at arbitrary points (include/gstark_poly.h, csrc/poly.hip; DESIGN 3.16).  Operands are Vectors or arrays of
     // BigInts, results stay on the device.  A library without the entry points (the tests' double) has no host route here: the members throw
     _polyNeed(symbol) {

@@ -155,6 +155,12 @@ const FnDesc kFns[] = {
     {"gs_poly_div", "cbipupupp"},
     {"gs_poly_eval_points", "cbipupup"},
     {"gs_poly_interpolate_points", "cbippupp"},
+    // include/gstark_sqrt.h: OPTIONAL in the same way; `roots_out` and `parities` may be 0 (flags only / every y even); the plan's four
+    // results are host uint32 (Buffers of 4 bytes)
+    {"gs_field_sqrt", "cpupp"},
+    {"gs_curve_lift_x", "cbbppupp"},
+    {"gs_curve_compress", "cpupp"},
+    {"gs_field_sqrt_plan", "coooo"},
     // include/gstark_diagnose.h: OPTIONAL in the same way; the three results are host arrays of `rows` uint64 each (Buffers of 8 * rows bytes)
     {"gs_nonzero_spans", "cpuuuooo"},
     {"gs_pseudorandom_indexes", "biiuio"},
