@@ -237,6 +237,14 @@ _SQRT_SIGNATURES = {
 }
 SQRT_SYMBOLS = tuple(_SQRT_SIGNATURES)
 
+# include/gstark_absorb.h: records of any length hashed with either family's permutation; optional in the same way (genstark_amd/hades.py
+# and genstark_amd/rescue_hash.py compute on host integers where a library lacks the family)
+_ABSORB_SIGNATURES = {
+    'gs_hades_absorb': (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _u64, _u32, _u32, _vp]),
+    'gs_rescue_absorb': (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
+}
+ABSORB_SYMBOLS = tuple(_ABSORB_SIGNATURES)
+
 # include/gstark_diagnose.h: the scan of the statement diagnosis; optional in the same way (a driver bound to a library without it
 # downloads the matrix and scans it on the host)
 _DIAGNOSE_SIGNATURES = {
@@ -261,7 +269,7 @@ def load_library(path):
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
                               + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_SPARSE_TREE_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
                               + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_POLY_SIGNATURES.items()) + list(_SQRT_SIGNATURES.items())
-                              + list(_DIAGNOSE_SIGNATURES.items())):
+                              + list(_ABSORB_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -12,11 +12,14 @@
 //               separates the levels.  Nothing here synchronises between workgroups.
 //   updates,    gs_hades_merkle_update and gs_hades_sparse_create hand hades_node_hash — launch_hash over rows of two nodes — to the
 //   sparse      drivers of field_tree.h, so an updated node is the node the tree build computes.
+//   records     gs_hades_absorb (include/gstark_absorb.h): one thread absorbs one row of any length, a permutation per `rate` elements
+//               (k_hades_absorb), the state in registers throughout; the row is read in place, by rows or by columns.
 //   path roots  gs_hades_merkle_path_roots (tree_verify.h): one thread walks one path through all its levels in ONE launch
 //               (k_hades_path_roots), the running node in registers; the sibling of a level is read straight from the path array.
 #include "field_tree.h"
 #include "tree_verify.h"
 #include "../../include/gstark_hades.h"
+#include "../../include/gstark_absorb.h"
 #include "../../include/gstark_tree_update.h"
 #include "../../include/gstark_tree_verify.h"
 #include "../../include/gstark_sparse_tree.h"
@@ -154,7 +157,55 @@ __global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_path_roots(const fe *_
     if (digest > 1) roots[k * digest + 1] = v1;
 }
 
+// Records of any length (include/gstark_absorb.h): thread k absorbs row k, `rate` elements per permutation, the state in registers from
+// the first block to the digest.  state[rate] starts as the length; every index into the state is a constant (the comparisons with
+// `rate` are the same in every lane).  Element i of the row is read at row[i * elem_stride] straight from memory, as k_hades_path_roots
+// reads its siblings: a block is 16 .. 224 bytes per thread against the hundreds to thousands of products of its permutation.  In the
+// columns layout (row_stride 1) consecutive lanes read consecutive elements; in the rows layout a thread's elements are consecutive
+// and the line one block fetches serves the next blocks from the cache.  The next block is NOT loaded ahead of the permutation: the
+// state and the S-box temporaries already set the register count.  A grid-stride loop: the grid is capped, nothing crosses lanes.
+template <int W>
+__global__ __launch_bounds__(GS_HADES_BLOCK) void k_hades_absorb(const fe *__restrict__ in, uint64_t count, uint32_t length, uint64_t row_stride, uint64_t elem_stride,
+                                                                 uint32_t rate, uint32_t digest, const fe *__restrict__ consts, uint32_t rf, uint32_t rp, uint64_t alpha,
+                                                                 fe *__restrict__ out) {
+#pragma unroll 1
+    for (uint64_t k = (uint64_t)blockIdx.x * GS_HADES_BLOCK + threadIdx.x; k < count; k += (uint64_t)gridDim.x * GS_HADES_BLOCK) {
+        const fe *__restrict__ row = in + k * row_stride;
+        fe s[W];
+#pragma unroll
+        for (int j = 0; j < W; j++) s[j] = j == (int)rate ? fe_make(length, 0, 0, 0) : fe_zero();
+#pragma unroll 1
+        for (uint32_t first = 0; first < length; first += rate) {
+#pragma unroll
+            for (int j = 0; j < W - 1; j++)
+                if (j < (int)rate && first + j < length) s[j] = fe_add(s[j], row[(uint64_t)(first + j) * elem_stride]);
+            hades_permute<W>(s, consts, rf, rp, alpha);
+        }
+        out[k * digest] = s[0];
+        if (digest > 1) out[k * digest + 1] = s[1];
+    }
+}
+
 namespace {
+
+#define GS_HADES_ABSORB_GRID (1u << 22)      // workgroups of k_hades_absorb at most: 2^30 threads, the rows beyond them by the stride loop
+
+int launch_absorb(gs_ctx *c, const gs_hades *h, const fe *in, uint64_t count, uint32_t length, uint64_t row_stride, uint64_t elem_stride, uint32_t rate, uint32_t digest,
+                  fe *out) {
+    uint64_t blocks = (count + GS_HADES_BLOCK - 1) / GS_HADES_BLOCK;
+    if (blocks > GS_HADES_ABSORB_GRID) blocks = GS_HADES_ABSORB_GRID;
+    switch (h->width) {
+#define X(W)                                                                                                                                         \
+    case W:                                                                                                                                          \
+        hipLaunchKernelGGL(k_hades_absorb<W>, dim3((unsigned)blocks), dim3(GS_HADES_BLOCK), 0, c->stream, in, count, length, row_stride, elem_stride, rate, digest, \
+                           (const fe *)h->consts, h->rf, h->rp, h->alpha, out);                                                                      \
+        break;
+        GS_SPONGE_WIDTHS(X)
+#undef X
+    }
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
 
 int launch_hash(gs_ctx *c, const gs_hades *h, const fe *in, uint64_t count, uint32_t arity, uint32_t digest, fe *out) {
     const uint64_t blocks = (count + GS_HADES_BLOCK - 1) / GS_HADES_BLOCK;
@@ -253,6 +304,17 @@ int gs_hades_hash(gs_ctx *c, const gs_hades *h, const void *in, uint64_t count, 
     if (!in || !out) return GS_ERR_ARG;
     gs_traffic(c, count * (arity + digest) * GS_ELT, count * hades_products(h), "k_hades_hash<%u>", h->width);
     return launch_hash(c, h, (const fe *)in, count, arity, digest, (fe *)out);
+}
+
+int gs_hades_absorb(gs_ctx *c, const gs_hades *h, const void *in, uint64_t count, uint32_t length, uint64_t row_stride, uint64_t elem_stride, uint32_t rate, uint32_t digest,
+                    void *out) {
+    int rc;
+    uint64_t blocks = 0;
+    if ((rc = sponge_check_handle(c, h, "hades_absorb")) ||
+        (rc = sponge_check_absorb(c, "hades_absorb", h->width, count, length, row_stride, elem_stride, rate, digest, in, out, &blocks)) || !count)
+        return rc;
+    gs_traffic(c, count * (length + digest) * GS_ELT, count * blocks * hades_products(h), "k_hades_absorb<%u>", h->width);
+    return launch_absorb(c, h, (const fe *)in, count, length, row_stride, elem_stride, rate, digest, (fe *)out);
 }
 
 int gs_hades_merkle(gs_ctx *c, const gs_hades *h, const void *leaves, uint64_t n, uint32_t digest, void *nodes_out) {

@@ -21,11 +21,14 @@
 //               Nothing here synchronises between workgroups.
 //   updates,    gs_rescue_merkle_update and gs_rescue_sparse_create hand rescue_node_hash — what a level of the tree build runs:
 //   sparse      launch_hash with the form pick_form chooses — to the drivers of field_tree.h: an updated node is the node the build computes.
+//   records     gs_rescue_absorb (include/gstark_absorb.h): a row of any length, a permutation per `rate` elements, in form 2 only
+//               (k_rescue_absorb<G>: a group of G lanes per row, the state in the lanes' registers from the first block to the digest).
 //   path roots  gs_rescue_merkle_path_roots (tree_verify.h): a path is a dependent chain of permutations, so it is walked in form 2
 //               only (k_rescue_path_roots<G>: a group of G lanes per path, every level in ONE launch); the entry's cap is form 2's limit.
 #include "field_tree.h"
 #include "tree_verify.h"
 #include "../../include/gstark_rescue.h"
+#include "../../include/gstark_absorb.h"
 #include "../../include/gstark_tree_update.h"
 #include "../../include/gstark_sparse_tree.h"
 #include "../../include/gstark_tree_verify.h"
@@ -244,6 +247,48 @@ __global__ __launch_bounds__(GS_RESCUE_BLOCK) void k_rescue_path_roots(const fe 
     if (live && j == 0) roots[k] = x;
 }
 
+// Records of any length (include/gstark_absorb.h), in form 2 as the path walk: an aligned group of G lanes absorbs one row, lane j
+// holding element j of the state from the first block to the digest.  Lane `rate` starts as the length, every other lane as zero; for
+// every block lane j < rate adds its element of the block (none past the end of the row), then the group permutes as k_rescue_spread
+// does.  Every lane stays active to the end — the cross-lane reads need the whole wave —, only the loads and the store are guarded.
+// A grid-stride loop whose trip count is that of the whole wave (a workgroup is one wave): the grid is capped.
+template <int G>
+__global__ __launch_bounds__(GS_RESCUE_BLOCK) void k_rescue_absorb(const fe *__restrict__ in, uint64_t count, uint32_t length, uint64_t row_stride, uint64_t elem_stride,
+                                                                   uint32_t rate, uint32_t digest, uint32_t modified, uint32_t width, const fe *__restrict__ consts,
+                                                                   uint32_t rounds, uint64_t alpha, const uint32_t *__restrict__ sched, uint32_t nops, uint32_t table,
+                                                                   fe *__restrict__ out) {
+    const uint32_t lane = threadIdx.x, j = lane % G, base = lane - j;
+    const uint32_t col = j < width ? j : 0;                                 // a surplus lane reads keys that exist and multiplies them by nothing
+    const fe *__restrict__ mds = consts + (uint64_t)(2 * rounds + 3) * width;
+    fe row[G];
+#pragma unroll
+    for (int i = 0; i < G; i++) row[i] = (j < width && i < (int)width) ? mds[j * width + i] : fe_zero();
+    uint32_t halves, first_key, first_inverse;
+    rescue_shape(rounds, modified, halves, first_key, first_inverse);
+#pragma unroll 1
+    for (uint64_t first_row = (uint64_t)blockIdx.x * (GS_RESCUE_BLOCK / G); first_row < count; first_row += (uint64_t)gridDim.x * (GS_RESCUE_BLOCK / G)) {
+        const uint64_t k = first_row + lane / G;
+        const bool live = k < count;
+        const fe *__restrict__ mine = in + (live ? k : 0) * row_stride;
+        fe x = j == rate ? fe_make(length, 0, 0, 0) : fe_zero();
+#pragma unroll 1
+        for (uint32_t first = 0; first < length; first += rate) {
+            if (live && j < rate && first + j < length) x = fe_add(x, mine[(uint64_t)(first + j) * elem_stride]);
+            if (!modified) x = fe_add(x, consts[col]);
+            uint32_t key = first_key, inverse = first_inverse;
+#pragma unroll 1
+            for (uint32_t h = 0; h < halves; h++, key++, inverse ^= 1u) {
+                x = inverse ? rescue_inv_sbox<rescue_chain>(x, sched, nops, table) : fe_pow_u64(x, alpha);
+                fe acc = consts[(uint64_t)key * width + col];
+#pragma unroll
+                for (int i = 0; i < G; i++) acc = fe_add(acc, fe_mul(row[i], rescue_lane_read(x, (int)(base + i))));
+                x = j < width ? acc : fe_zero();
+            }
+        }
+        if (live && j < digest) out[k * digest + j] = x;
+    }
+}
+
 namespace {
 
 uint32_t spread_group(const gs_rescue *h) { return h->width <= 2 ? 2u : (h->width <= 4 ? 4u : 8u); }
@@ -255,6 +300,25 @@ int launch_path_roots(gs_ctx *c, const gs_rescue *h, const fe *paths, uint32_t d
     hipLaunchKernelGGL(k_rescue_path_roots<G>, dim3((unsigned)blocks), dim3(GS_RESCUE_BLOCK), 0, c->stream, paths, depth, idx, leaves, count, h->width, \
                        (const fe *)h->consts, h->rounds, h->alpha, h->sched, h->nops, h->table, roots)
     if (g == 4) X(4);
+    else X(8);
+#undef X
+    GS_LAUNCH_CHECK(c);
+    return GS_OK;
+}
+
+#define GS_RESCUE_ABSORB_GRID (1u << 24)     // workgroups of k_rescue_absorb at most: 2^30 lanes, the rows beyond them by the stride loop
+
+int launch_absorb(gs_ctx *c, const gs_rescue *h, const fe *in, uint64_t count, uint32_t length, uint64_t row_stride, uint64_t elem_stride, uint32_t rate, uint32_t digest,
+                  uint32_t modified, fe *out) {
+    const uint32_t g = spread_group(h);
+    const uint64_t per = GS_RESCUE_BLOCK / g;
+    uint64_t blocks = (count + per - 1) / per;
+    if (blocks > GS_RESCUE_ABSORB_GRID) blocks = GS_RESCUE_ABSORB_GRID;
+#define X(G)                                                                                                                                          \
+    hipLaunchKernelGGL(k_rescue_absorb<G>, dim3((unsigned)blocks), dim3(GS_RESCUE_BLOCK), 0, c->stream, in, count, length, row_stride, elem_stride, rate, digest, \
+                       modified, h->width, (const fe *)h->consts, h->rounds, h->alpha, h->sched, h->nops, h->table, out)
+    if (g == 2) X(2);
+    else if (g == 4) X(4);
     else X(8);
 #undef X
     GS_LAUNCH_CHECK(c);
@@ -391,6 +455,17 @@ int gs_rescue_hash(gs_ctx *c, const gs_rescue *h, const void *in, uint64_t count
     form = pick_form(count, form);
     traffic(c, h, count, arity, digest, modified, form);
     return launch_hash(c, h, (const fe *)in, count, arity, digest, modified, form, (fe *)out);
+}
+
+int gs_rescue_absorb(gs_ctx *c, const gs_rescue *h, const void *in, uint64_t count, uint32_t length, uint64_t row_stride, uint64_t elem_stride, uint32_t rate,
+                     uint32_t digest, uint32_t modified, void *out) {
+    int rc;
+    uint64_t blocks = 0;
+    if ((rc = sponge_check_handle(c, h, "rescue_absorb"))) return rc;
+    if (modified > 1) return gs_fail(c, GS_ERR_ARG, "rescue_absorb: modified is 0 (sponge) or 1 (modifiedSponge), not %u", modified);
+    if ((rc = sponge_check_absorb(c, "rescue_absorb", h->width, count, length, row_stride, elem_stride, rate, digest, in, out, &blocks)) || !count) return rc;
+    gs_traffic(c, count * (length + digest) * GS_ELT, count * blocks * rescue_products(h, modified), "k_rescue_absorb<%u>", spread_group(h));
+    return launch_absorb(c, h, (const fe *)in, count, length, row_stride, elem_stride, rate, digest, modified, (fe *)out);
 }
 
 int gs_rescue_merkle(gs_ctx *c, const gs_rescue *h, const void *leaves, uint64_t n, void *nodes_out) {

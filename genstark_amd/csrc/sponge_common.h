@@ -57,6 +57,31 @@ static inline int sponge_check_count(gs_ctx *c, const char *who, uint64_t count)
     return count <= (1ull << 36) ? GS_OK : gs_fail(c, GS_ERR_ARG, "%s: at most 2^36 permutations per call", who);
 }
 
+// An absorb launch (include/gstark_absorb.h): `count` rows of `length` elements at in[k * row_stride + i * elem_stride], `rate` of them
+// per permutation of a state of `width`, `digest` elements out each.  Every refusal has a message of its own; -> *blocks: the
+// permutations of one row.  The caller has checked its handle, and returns GS_OK itself when count is 0 (nothing below looks at the
+// pointers of an empty call).
+#define GS_ABSORB_MAX_LENGTH (1u << 16)
+static inline int sponge_check_absorb(gs_ctx *c, const char *who, uint32_t width, uint64_t count, uint32_t length, uint64_t row_stride, uint64_t elem_stride, uint32_t rate,
+                                      uint32_t digest, const void *in, const void *out, uint64_t *blocks) {
+    if (rate < 1 || rate >= width) return gs_fail(c, GS_ERR_ARG, "%s: a rate of %u does not leave a capacity in a state of %u (1 .. %u)", who, rate, width, width - 1);
+    if (digest < 1 || digest > 2 || digest > rate) return gs_fail(c, GS_ERR_ARG, "%s: a digest of 1 or 2 elements and at most the rate (%u), not %u", who, rate, digest);
+    if (length < 1 || length > GS_ABSORB_MAX_LENGTH) return gs_fail(c, GS_ERR_ARG, "%s: a row of %u elements (1 .. 65536)", who, length);
+    if (fe_ge_p(fe_from_u64(length))) return gs_fail(c, GS_ERR_ARG, "%s: a row of %u elements: the length is below the modulus", who, length);
+    const bool by_rows = elem_stride == 1 && row_stride >= length, by_columns = row_stride == 1 && elem_stride >= count;
+    if (!by_rows && !by_columns)
+        return gs_fail(c, GS_ERR_ARG, "%s: strides (%llu, %llu) are neither rows (elem_stride 1, row_stride >= length) nor columns (row_stride 1, elem_stride >= count)", who,
+                       (unsigned long long)row_stride, (unsigned long long)elem_stride);
+    *blocks = (length + rate - 1) / rate;
+    if (count > (1ull << 36) / *blocks) return gs_fail(c, GS_ERR_ARG, "%s: at most 2^36 permutations per call", who);
+    if (!count) return GS_OK;
+    if (!in || !out) return gs_fail(c, GS_ERR_ARG, "%s: in and out are required", who);
+    const unsigned __int128 read = ((unsigned __int128)(count - 1) * row_stride + (unsigned __int128)(length - 1) * elem_stride + 1) * GS_ELT;
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    if (b < a + read && a < b + count * digest * GS_ELT) return gs_fail(c, GS_ERR_ARG, "%s: out overlaps in", who);
+    return GS_OK;
+}
+
 static inline int sponge_check_leaves(gs_ctx *c, const char *who, uint64_t n) {
     return n >= 2 && gs_is_pow2(n) && n <= (1ull << 36) ? GS_OK : gs_fail(c, GS_ERR_ARG, "%s: the number of leaves is a power of two, 2 .. 2^36", who);
 }

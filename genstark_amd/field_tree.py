@@ -60,6 +60,76 @@ class DeviceParameters:
         return out
 
 
+    # ---- records of any length (include/gstark_absorb.h) ---------------------------------------------------------------------------
+    def _absorbShape(self, digest, rate):
+        """the rate (default: width - 1 up to a state of 3, width - 2 above) after the refusals that need no input"""
+        rate = (self.width - 1 if self.width <= 3 else self.width - 2) if rate is None else int(rate)
+        if not 1 <= rate < self.width:
+            raise GstarkError(f'{self._who}: absorb: a rate of {rate} does not leave a capacity in a state of {self.width} (1 .. {self.width - 1})')
+        if digest not in (1, 2) or digest > rate:
+            raise GstarkError(f'{self._who}: absorb: a digest of 1 or 2 elements and at most the rate ({rate}), not {digest}')
+        return rate
+
+    def _absorbLength(self, length):
+        if not 1 <= length <= ABSORB_MAX_LENGTH:
+            raise GstarkError(f'{self._who}: absorb: a record of {length} elements (1 .. {ABSORB_MAX_LENGTH})')
+
+    def _absorbHost(self, inputs, digest, rate, permute):
+        """the definition on host integers: the length in the first capacity element, `rate` inputs added per permutation"""
+        p = self.field.modulus
+        inputs = [int(v) % p for v in inputs]
+        self._absorbLength(len(inputs))
+        state = [0] * self.width
+        state[rate] = len(inputs) % p
+        for at in range(0, len(inputs), rate):
+            for j, v in enumerate(inputs[at:at + rate]):
+                state[j] = (state[j] + v) % p
+            state = permute(state)
+        return state[:digest]
+
+    def _absorbRows(self, rows, digest, rate, columns, permute, *options):
+        """absorbMany: `options` is what gs_<family>_absorb takes between `digest` and `out`.  rows: a device Matrix (count x L, or
+        L x count with columns=True), equal-length lists of integers, or with columns=True a list of L Vectors of one length."""
+        f = self.field
+        rate = self._absorbShape(digest, rate)
+        if not isinstance(rows, Matrix):
+            rows = list(rows)
+            if columns and rows and all(isinstance(r, Vector) for r in rows):
+                if any(r.length != rows[0].length for r in rows):
+                    raise GstarkError(f'{self._who}: absorb: every column has the same number of elements')
+                rows = f.newMatrixFromVectors(rows) if rows[0].length else [[] for _ in rows]
+            else:
+                rows = [list(r) for r in rows]
+                if any(len(r) != len(rows[0]) for r in rows):
+                    raise GstarkError(f'{self._who}: absorb: every {"column" if columns else "row"} has the same number of elements')
+        if isinstance(rows, Matrix):
+            outer, inner = rows.rowCount, rows.colCount
+        else:
+            outer, inner = len(rows), len(rows[0]) if rows else 0
+            if not outer and not columns:
+                return Matrix(f.backend, 0, digest)
+        count, length = (inner, outer) if columns else (outer, inner)
+        self._absorbLength(length)
+        if not count:
+            return Matrix(f.backend, 0, digest)
+        entry = f'gs_{self._family}_absorb'
+        if not self.onDevice:
+            values = rows.toValues() if isinstance(rows, Matrix) else rows
+            if columns:
+                values = [list(r) for r in zip(*values)]
+            return f.newMatrixFrom([self._absorbHost(r, digest, rate, permute) for r in values])
+        if not hasattr(f.backend.lib, entry):                                # a hash that lives on the device absorbs there: no quiet host path
+            raise GstarkError(f'{self._who}: the library has no {entry} (include/gstark_absorb.h)')
+        src = rows if isinstance(rows, Matrix) else f.newMatrixFrom(rows)
+        out = Matrix(f.backend, count, digest)
+        row_stride, elem_stride = (1, count) if columns else (length, 1)
+        f.backend.call(entry, self.handle(), C.c_void_p(src.ptr), count, length, row_stride, elem_stride, rate, digest, *options, C.c_void_p(out.ptr))
+        return out
+
+
+ABSORB_MAX_LENGTH = 1 << 16                  # the longest record of absorb / absorbMany
+
+
 def path_root(index, proof, node):
     """the root a path (the leaf, then its siblings bottom-up) implies: node(left, right) level by level, sides by the index bits"""
     index += 1 << (len(proof) - 1)

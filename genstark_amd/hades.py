@@ -68,6 +68,19 @@ class HadesHash(DeviceParameters):
         """One permutation per row of `rows` (a device Matrix, or rows of integers of one length): a Matrix of len(rows) x digest."""
         return self._hashRows(rows, digest, self.hash)
 
+    def absorb(self, inputs, digest=2, rate=None):
+        """The digest of a record of any length (1 .. 2^16 values) on host integers: state = zeros with state[rate] = len(inputs); per
+        block of `rate` inputs, the block is ADDED to state[0 .. rate) and the state permuted; the first `digest` elements of the last
+        state.  rate defaults to width - 1 up to a state of 3 and to width - 2 above.  On purpose this is NOT hash(inputs) for short
+        inputs: the length in the capacity keeps [a] and [a, 0] apart."""
+        return self._absorbHost(list(inputs), digest, self._absorbShape(digest, rate), self.permute)
+
+    def absorbMany(self, rows, digest=2, rate=None, columns=False):
+        """absorb(row) for every row, one launch (gs_hades_absorb, include/gstark_absorb.h): a Matrix of count x digest.  rows: a device
+        Matrix of count x L, or lists of one length; with columns=True the register-major L x count Matrix of a trace, or a list of L
+        Vectors of one length (put side by side as evalPolysAtPoints does): record k is column k.  Like absorb, not hashMany of short rows."""
+        return self._absorbRows(rows, digest, rate, columns, self.permute)
+
 
 class HadesMerkleTree(FieldMerkleTree):
     """MerkleTree (digest=2) / MerkleTree2 (digest=1) of utils.ts over `hash`: 2n x digest elements in the heap layout, leaves at

@@ -136,6 +136,55 @@ def _merkle_transition(r, k):                 # lib128.aa:48-77 ($merkleTransiti
     return [x * k[5] + (y * ((1 - k[5]) * k[6]) + z * ((1 - k[5]) * (1 - k[6]))) for x, y, z in zip(a, b, h1 + h2)]
 
 
+ABSORB_RATE = STATE_WIDTH - 2               # the default rate of poseidon(field).absorb: four elements per permutation
+
+
+def compute_poseidon_absorb_air(field, blocks, extensionFactor=32):
+    """Knowledge of a record of PUBLIC length L whose digest is poseidon(field).absorb(record): 6 registers, 64 * blocks steps, blocks =
+    ceil(L / 4) a power of two.  prove(assertions, inputs, first) takes what poseidon_absorb_inputs() returns.  The four secret input
+    registers hold the record's blocks (zero-padded, each held 64 steps, shifted by -1 as `held` builds them); on the last step of a
+    block (mask 1) the transition ADDS the next block to registers 0 .. 3 instead of running a round, every other step is a round of
+    the permutation.  The first row is [m0, m1, m2, m3, L, 0]: the first block already added, the length in the first capacity
+    register.  The statement is made by the assertions: register 4 = L and register 5 = 0 at step 0, registers 0 and 1 = the digest at
+    the last step; registers 0 .. 3 of the first row stay secret.  (The mask is 1 on the very last step too: the row after it is the
+    first row again, nothing constrains it.)"""
+    if blocks < 1 or blocks & (blocks - 1):
+        raise ValueError(f'compute_poseidon_absorb_air: {blocks} blocks: the number of blocks, ceil(L / {ABSORB_RATE}), is a power of two')
+    total = ROUND_STEPS * blocks
+    public = [segment_mask(ROUND_STEPS), round_controls()] + round_constant_columns(field)      # k[0] mask, k[1] round kind, k[2..7] round constants
+    npub = len(public)
+
+    def transition(r, k):
+        block, mask = list(k[npub:npub + ABSORB_RATE]) + [0, 0], k[0]
+        rnd = poseidon_round(r, k[2:8], k[1])
+        return [(x + b) * mask + y * (1 - mask) for x, b, y in zip(r, block, rnd)]
+
+    def evaluation(r, n, k):
+        return [a - b for a, b in zip(n, transition(r, k))]
+
+    return GenericAir(total, STATE_WIDTH, [7] * STATE_WIDTH, public, transition, evaluation, lambda seed: list(seed), extensionFactor, field,
+                      secretRegisters=ABSORB_RATE)
+
+
+def poseidon_absorb_inputs(field, record):
+    """(inputs, first, assertions) of compute_poseidon_absorb_air(field, ceil(len(record) / 4)): the four secret columns, the first row
+    and the assertions of the statement `a record of len(record) elements has the digest poseidon(field).absorb(record)`."""
+    p = field.modulus
+    record = [int(v) % p for v in record]
+    length = len(record)
+    blocks = -(-length // ABSORB_RATE)
+    if blocks < 1 or blocks & (blocks - 1):
+        raise ValueError(f'poseidon_absorb_inputs: a record of {length} elements is {blocks} blocks: the number of blocks, ceil(L / {ABSORB_RATE}), is a power of two')
+    total = ROUND_STEPS * blocks
+    padded = record + [0] * (ABSORB_RATE * blocks - length)
+    inputs = [held([padded[ABSORB_RATE * b + j] for b in range(blocks)], ROUND_STEPS, total) for j in range(ABSORB_RATE)]
+    first = padded[:ABSORB_RATE] + [length % p, 0]
+    digest = poseidon(field).absorb(record, 2, ABSORB_RATE)
+    assertions = [{'step': 0, 'register': 4, 'value': length % p}, {'step': 0, 'register': 5, 'value': 0},
+                  {'step': total - 1, 'register': 0, 'value': digest[0]}, {'step': total - 1, 'register': 1, 'value': digest[1]}]
+    return inputs, first, assertions
+
+
 def compute_merkle_update_air(field, depth, extensionFactor=32):
     """lib128.aa:152-203 (ComputeMerkleUpdate): the authentication paths of an old and a new leaf at the same (SECRET) index run
     side by side — 24 registers, 24 transition constraints + `bit^2 = bit`.  Secret columns from merkle_update_inputs(); the old
@@ -205,21 +254,24 @@ class PoseidonMerkleTree:
         return proof
 
 
-def poseidon_tree(field, leaves):
-    """The same tree built on the device (genstark_amd/hades.py: HadesMerkleTree over lib128's matrix and `prng` round constants):
-    leaves as above, or a device Matrix of n x 2.  `root`, `prove(index)` and `nodes` are PoseidonMerkleTree's."""
-    from .hades import HadesHash, HadesMerkleTree
+def poseidon(field):
+    """The library's hash as a HadesHash (genstark_amd/hades.py): width 6, x^5, 8 + 55 rounds, lib128's matrix and `prng` round constants."""
+    from .hades import HadesHash
     cols = round_constant_columns(field)
     rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
-    return HadesMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, STATE_WIDTH, rc, MDS), leaves, 2)
+    return HadesHash(field, 5, F_ROUNDS, P_ROUNDS, STATE_WIDTH, rc, MDS)
+
+
+def poseidon_tree(field, leaves):
+    """The same tree built on the device (genstark_amd/hades.py: HadesMerkleTree over poseidon(field)): leaves as above, or a device
+    Matrix of n x 2.  `root`, `prove(index)` and `nodes` are PoseidonMerkleTree's."""
+    from .hades import HadesMerkleTree
+    return HadesMerkleTree(poseidon(field), leaves, 2)
 
 
 def poseidon_sparse_tree(field, depth, empty=None, slots_hint=1024):
     """The sparse tree of 2^depth leaves (depth 1 .. 36) over the same hash (genstark_amd/sparse_tree.py: HadesSparseMerkleTree): every
     leaf holds `empty` (default: zeros) until set, and root, paths and update records are those of poseidon_tree(field, [empty] * 2^depth).
     Its records feed compute_merkle_update_air(field, depth) at depths no dense tree can hold."""
-    from .hades import HadesHash
     from .sparse_tree import HadesSparseMerkleTree
-    cols = round_constant_columns(field)
-    rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
-    return HadesSparseMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, STATE_WIDTH, rc, MDS), depth, 2, empty, slots_hint)
+    return HadesSparseMerkleTree(poseidon(field), depth, 2, empty, slots_hint)

@@ -182,13 +182,19 @@ class PoseidonMerkleTree:
         return proof
 
 
-def poseidon_tree(field, leaves):
-    """The same tree built on the device (genstark_amd/hades.py: HadesMerkleTree over lib224's matrix and `prng` round constants):
-    leaves as above, or a device Vector of n elements.  `root`, `prove(index)` and `nodes` are PoseidonMerkleTree's."""
-    from .hades import HadesHash, HadesMerkleTree
+def poseidon(field):
+    """The library's hash as a HadesHash (genstark_amd/hades.py): width 3, x^5, 8 + 55 rounds, lib224's matrix and `prng` round constants."""
+    from .hades import HadesHash
     cols = round_constant_columns(field)
     rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
-    return HadesMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, WIDTH, rc, MDS), leaves, 1)
+    return HadesHash(field, 5, F_ROUNDS, P_ROUNDS, WIDTH, rc, MDS)
+
+
+def poseidon_tree(field, leaves):
+    """The same tree built on the device (genstark_amd/hades.py: HadesMerkleTree over poseidon(field)): leaves as above, or a device
+    Vector of n elements.  `root`, `prove(index)` and `nodes` are PoseidonMerkleTree's."""
+    from .hades import HadesMerkleTree
+    return HadesMerkleTree(poseidon(field), leaves, 1)
 
 
 # ---- Schnorr signature verification ---------------------------------------------------------------------------------------------
@@ -259,8 +265,5 @@ def poseidon_sparse_tree(field, depth, empty=None, slots_hint=1024):
     """The sparse tree of 2^depth leaves (depth 1 .. 36) over the same hash (genstark_amd/sparse_tree.py: HadesSparseMerkleTree): every
     leaf holds `empty` (default: zeros) until set, and root, paths and update records are those of poseidon_tree(field, [empty] * 2^depth).
     Its records feed compute_merkle_update_air(field, depth) at depths no dense tree can hold."""
-    from .hades import HadesHash
     from .sparse_tree import HadesSparseMerkleTree
-    cols = round_constant_columns(field)
-    rc = [[col[i] for col in cols] for i in range(F_ROUNDS + P_ROUNDS)]
-    return HadesSparseMerkleTree(HadesHash(field, 5, F_ROUNDS, P_ROUNDS, WIDTH, rc, MDS), depth, 1, empty, slots_hint)
+    return HadesSparseMerkleTree(poseidon(field), depth, 1, empty, slots_hint)

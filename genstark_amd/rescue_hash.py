@@ -137,6 +137,24 @@ class RescueHash(DeviceParameters):
         run = self.modifiedSponge if modified else self.sponge
         return self._hashRows(rows, digest, lambda r: run(r)[1][-1], 1 if modified else 0, form, check=check)
 
+    def _permutation(self, modified):
+        """what hashMany(modified=..) applies to a full-width row: the whole last state"""
+        run = self.modifiedSponge if modified else self.sponge
+        return lambda state: run(state)[1][-1]
+
+    def absorb(self, inputs, digest=1, rate=None, modified=True):
+        """The digest of a record of any length (1 .. 2^16 values) on host integers: state = zeros with state[rate] = len(inputs); per
+        block of `rate` inputs, the block is ADDED to state[0 .. rate) and the state permuted (modifiedSponge of the full state, or
+        sponge with modified=False); the first `digest` elements of the last state.  rate defaults to width - 1 up to a state of 3 and
+        to width - 2 above.  On purpose this is NOT the sponge of short inputs: the length in the capacity keeps [a] and [a, 0] apart."""
+        return self._absorbHost(list(inputs), digest, self._absorbShape(digest, rate), self._permutation(modified))
+
+    def absorbMany(self, rows, digest=1, rate=None, columns=False, modified=True):
+        """absorb(row) for every row, one launch (gs_rescue_absorb, include/gstark_absorb.h): a Matrix of count x digest.  rows: a device
+        Matrix of count x L, or lists of one length; with columns=True the register-major L x count Matrix of a trace, or a list of L
+        Vectors of one length: record k is column k.  Like absorb, not hashMany of short rows."""
+        return self._absorbRows(rows, digest, rate, columns, self._permutation(modified), 1 if modified else 0)
+
 
 class RescueMerkleTree(FieldMerkleTree):
     """MerkleTree of utils.ts:232-273 over hash.hash2: 2n elements in the heap layout, leaves at n .. 2n - 1, root at 1.  leaves: a device

@@ -58,6 +58,54 @@ function hashMany(field, symbol, handle, rows, digest, ...options) {
     return out;
 }
 
+/** throws when the field's library lacks `symbol` of include/gstark_absorb.h (optional in the same way) */
+function needAbsorb(field, symbol) {
+    if (!field.lib.has || !field.lib.has(symbol)) {
+        throw new Error(`the library of the field of ${field.modulus} elements has no ${symbol} entry point (include/gstark_absorb.h): records are not absorbed on this device library`);
+    }
+}
+
+/** the rate of absorb / absorbMany (default: width - 1 up to a state of 3, width - 2 above) after the refusals that need no input */
+function absorbRate(width, digest, rate) {
+    if (rate === undefined || rate === null) rate = width <= 3 ? width - 1 : width - 2;
+    if (!(Number.isInteger(rate) && rate >= 1 && rate < width)) throw new Error(`absorb: a rate of ${rate} does not leave a capacity in a state of ${width} (1 .. ${width - 1})`);
+    if (!((digest === 1 || digest === 2) && digest <= rate)) throw new Error(`absorb: a digest of 1 or 2 elements and at most the rate (${rate}), not ${digest}`);
+    return rate;
+}
+
+const ABSORB_MAX_LENGTH = 1 << 16;
+
+/** absorb on BigInts (include/gstark_absorb.h): state = zeros with state[rate] = the length; per block of `rate` inputs the block is
+ *  ADDED to state[0 .. rate) and the state permuted; the first `digest` elements of the last state */
+function absorbHost(field, width, permute, inputs, digest, rate) {
+    rate = absorbRate(width, digest, rate);
+    if (!(inputs.length >= 1 && inputs.length <= ABSORB_MAX_LENGTH)) throw new Error(`absorb: a record of ${inputs.length} elements (1 .. ${ABSORB_MAX_LENGTH})`);
+    let state = new Array(width).fill(0n);
+    state[rate] = field.mod(BigInt(inputs.length));
+    for (let at = 0; at < inputs.length; at += rate) {
+        for (let j = 0; j < rate && at + j < inputs.length; j++) state[j] = field.mod(state[j] + BigInt(inputs[at + j]));
+        state = permute(state);
+    }
+    return state.slice(0, digest);
+}
+
+/** absorb for every row of a device Matrix of count x L (or of rows of BigInts) in one launch — with `columns`, for every column of the
+ *  register-major L x count Matrix: a Matrix of count x digest, like hashMany; options: what `symbol` takes between `digest` and `out` */
+function absorbMany(field, symbol, handle, width, rows, digest, rate, columns, ...options) {
+    needAbsorb(field, symbol);
+    rate = absorbRate(width, digest, rate);
+    if (!(rows instanceof Matrix)) {
+        if (rows.some(r => r.length !== rows[0].length)) throw new Error(`absorb: every ${columns ? 'column' : 'row'} has the same number of elements`);
+        rows = field.newMatrixFrom(rows);
+    }
+    field._own(rows);
+    const count = columns ? rows.colCount : rows.rowCount, length = columns ? rows.rowCount : rows.colCount;
+    if (!(length >= 1 && length <= ABSORB_MAX_LENGTH)) throw new Error(`absorb: a record of ${length} elements (1 .. ${ABSORB_MAX_LENGTH})`);
+    const out = new Matrix(field, count, digest);
+    if (count) field.lib.call(symbol, field.ctx, handle(), rows.ptr, count, length, columns ? 1 : length, columns ? count : 1, rate, digest, ...options, out.ptr);
+    return out;
+}
+
 /** the tree over the device leaves `src` (the caller has checked that they are the field's: field._own), built by buildCall(handle, src, n, deviceNodes); newNodes(count): an array of the kind deviceNodes is;
  *  update: { symbol, call(handle, deviceNodes, n, indexes, leaves, count, before, roots) } — the family's entry of include/gstark_tree_update.h */
 class DeviceTree {
@@ -267,4 +315,4 @@ function installVerify(cls, family) {
     };
 }
 
-module.exports = { destroyRegistry, needDevice, needUpdate, needVerify, needSparse, lazyHandle, hashMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify };
+module.exports = { destroyRegistry, needDevice, needUpdate, needVerify, needSparse, lazyHandle, hashMany, absorbHost, absorbMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify };

@@ -2,6 +2,8 @@
 // js/hades.js — the Poseidon helpers of the reference's examples/poseidon/utils.ts with the bulk work on the device
 // (include/gstark_hades.h through the addon's table): createHash(field, exp, rf, rp, stateWidth, rc?) returns the example's hash function
 // (BigInt arithmetic on the host, as upstream) which also carries .hashMany(matrix, digest) — one permutation per row in one launch —,
+// .absorb(inputs, digest, rate) — a record of any length, on the host — and .absorbMany(rows, digest, rate, columns) — one record per
+// row, or per column, in one launch (include/gstark_absorb.h) —,
 // and MerkleTree / MerkleTree2 have the example's members (nodes, root, prove, static verify) plus proveMany(indexes) and update /
 // updateMany(indexes, leaves): the tree is built and updated by the device, the paths of any number of leaves and the witnesses of any
 // number of updates come back in one read-back; static pathRoots / verifyMany / verifyUpdates (include/gstark_tree_verify.h) check batches
@@ -9,7 +11,7 @@
 // library lacks the entry points (they are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const crypto = require('crypto');
 const { Matrix, Vector } = require('./galois.js');
-const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify } = require('./field_tree.js');
+const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, absorbHost, absorbMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify } = require('./field_tree.js');
 
 function constants(field, seed, count) {      // utils.ts:115-122
     const out = new Array(count);
@@ -42,17 +44,20 @@ function createHash(field, exp, rf, rp, stateWidth, rc, mds) {
     if (matrix.length !== m || matrix.some(row => row.length !== m)) throw new Error(`createHash: the matrix has ${m} rows of ${m} values`);
     const p = field.modulus;
 
-    const hash = function (inputs) {
-        if (!(inputs.length > 0 && inputs.length < m)) throw new Error(`hash: ${inputs.length} inputs do not fit a state of ${m}`);
-        let state = inputs.map(v => field.mod(BigInt(v)));
-        while (state.length < m) state.push(0n);
+    const permute = function (state) {
         for (let i = 0; i < rf + rp; i++) {
             state = state.map((s, j) => (s + ark[i][j]) % p);
             if (i < rf / 2 || i >= rf / 2 + rp) state = state.map(s => field.exp(s, alpha));
             else state[m - 1] = field.exp(state[m - 1], alpha);
             state = matrix.map(row => row.reduce((acc, a, j) => (acc + a * state[j]) % p, 0n));
         }
-        return state.slice(0, 2);
+        return state;
+    };
+    const hash = function (inputs) {
+        if (!(inputs.length > 0 && inputs.length < m)) throw new Error(`hash: ${inputs.length} inputs do not fit a state of ${m}`);
+        const state = inputs.map(v => field.mod(BigInt(v)));
+        while (state.length < m) state.push(0n);
+        return permute(state).slice(0, 2);
     };
     hash.field = field;
     hash.stateWidth = m;
@@ -64,6 +69,11 @@ function createHash(field, exp, rf, rp, stateWidth, rc, mds) {
         needDevice(field);
         return hashMany(field, 'gs_hades_hash', hash.handle(), rows, digest);
     };
+    /** the digest of a record of any length (BigInts, on the host): the length in the first capacity element, `rate` inputs ADDED per
+     *  permutation (include/gstark_absorb.h).  On purpose NOT hash(inputs) for short inputs: [a] and [a, 0] have different digests */
+    hash.absorb = (inputs, digest = 2, rate) => absorbHost(field, m, permute, inputs, digest, rate);
+    /** absorb for every row of a device Matrix of count x L (or of rows of BigInts), one launch; columns: every column of an L x count Matrix */
+    hash.absorbMany = (rows, digest = 2, rate, columns = false) => absorbMany(field, 'gs_hades_absorb', hash.handle, m, rows, digest, rate, columns);
     return hash;
 }
 

@@ -3,12 +3,13 @@
 // (include/gstark_rescue.h through the addon's table): createRescue(field, alpha, invAlpha, registers, rounds, mds, constants) has the
 // members of the example's Rescue class (unrollConstants, groupConstants, sponge, modifiedSponge: BigInt arithmetic on the host, as
 // upstream) and .hash2(v1, v2) = makeHashFunction, plus .hashMany(matrix, digest, modified, form) — one permutation per row in one
-// launch — and .merkleTree(values): the example's MerkleTree (nodes, root, prove, static verify) built by the device, with
+// launch —, .absorb(inputs, digest, rate, modified) and .absorbMany(rows, digest, rate, columns, modified) — records of any length, one
+// per row or per column (include/gstark_absorb.h) — and .merkleTree(values): the example's MerkleTree (nodes, root, prove, static verify) built by the device, with
 // proveMany(indexes) in one read-back and static pathRoots / verifyMany / verifyUpdates over the rescue object (include/gstark_tree_verify.h:
 // batches of paths and of update records checked on the device).  `field` is a PrimeField of js/galois.js.  A field whose library lacks the entry points (they
 // are optional on an implementation of the ABI) makes the device members throw an Error saying so.
 const { Vector } = require('./galois.js');
-const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify } = require('./field_tree.js');
+const { destroyRegistry, needDevice: needDeviceOf, lazyHandle, hashMany, absorbHost, absorbMany, DeviceTree, SparseDeviceTree, verifyPath, installVerify } = require('./field_tree.js');
 
 const registry = destroyRegistry('gs_rescue_destroy');
 const needDevice = field => needDeviceOf(field, 'rescue', 'Rescue');
@@ -95,6 +96,17 @@ function createRescue(field, alpha, invAlpha, registers, rounds, mds, constants)
         hashMany(rows, digest = 1, modified = true, form = 0) {
             needDevice(field);
             return hashMany(field, 'gs_rescue_hash', rescue.handle(), rows, digest, modified ? 1 : 0, form);
+        },
+        /** the digest of a record of any length (BigInts, on the host): the length in the first capacity element, `rate` inputs ADDED per
+         *  permutation — the whole last state of modifiedSponge, or of sponge (include/gstark_absorb.h).  On purpose NOT the sponge of
+         *  short inputs: [a] and [a, 0] have different digests */
+        absorb(inputs, digest = 1, rate, modified = true) {
+            const permute = state => { const t = (modified ? rescue.modifiedSponge(state) : rescue.sponge(state)).trace; return t[t.length - 1]; };
+            return absorbHost(field, m, permute, inputs, digest, rate);
+        },
+        /** absorb for every row of a device Matrix of count x L (or of rows of BigInts), one launch; columns: every column of an L x count Matrix */
+        absorbMany(rows, digest = 1, rate, columns = false, modified = true) {
+            return absorbMany(field, 'gs_rescue_absorb', rescue.handle, m, rows, digest, rate, columns, modified ? 1 : 0);
         },
         merkleTree(values) { return new MerkleTree(values, rescue); },
         /** the sparse tree of 2^depth leaves (depth 1 .. 36) that all hold `empty` until set (include/gstark_sparse_tree.h) */

@@ -161,6 +161,9 @@ const FnDesc kFns[] = {
     {"gs_curve_lift_x", "cbbppupp"},
     {"gs_curve_compress", "cpupp"},
     {"gs_field_sqrt_plan", "coooo"},
+    // include/gstark_absorb.h: OPTIONAL in the same way; the handles are those of gs_hades_create / gs_rescue_create
+    {"gs_hades_absorb", "cppuiuuiip"},
+    {"gs_rescue_absorb", "cppuiuuiiip"},
     // include/gstark_diagnose.h: OPTIONAL in the same way; the three results are host arrays of `rows` uint64 each (Buffers of 8 * rows bytes)
     {"gs_nonzero_spans", "cpuuuooo"},
     {"gs_pseudorandom_indexes", "biiuio"},
