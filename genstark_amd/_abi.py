@@ -237,6 +237,16 @@ _SQRT_SIGNATURES = {
 }
 SQRT_SYMBOLS = tuple(_SQRT_SIGNATURES)
 
+# include/gstark_scan.h: running sums, running products and linear recurrences over device vectors; optional in the same way
+# (genstark_amd/field.py computes on host integers where a library lacks them)
+_SCAN_SIGNATURES = {
+    'gs_scan': (_int, [_vp, _int, _int, _vp, _vp, _u64, _u64, _vp, _vp]),
+    'gs_scan_affine': (_int, [_vp, _int, _vp, _bytes, _vp, _bytes, _vp, _u64, _u64, _vp]),
+    'gs_reduce': (_int, [_vp, _int, _vp, _u64, _u64, _vp]),
+    'gs_scan_plan': (_int, [_vp, _u64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_u32)]),
+}
+SCAN_SYMBOLS = tuple(_SCAN_SIGNATURES)
+
 # include/gstark_absorb.h: records of any length hashed with either family's permutation; optional in the same way (genstark_amd/hades.py
 # and genstark_amd/rescue_hash.py compute on host integers where a library lacks the family)
 _ABSORB_SIGNATURES = {
@@ -269,6 +279,7 @@ def load_library(path):
     for name, (res, args) in (list(_OPTIONAL_SIGNATURES.items()) + list(_HADES_SIGNATURES.items()) + list(_RESCUE_SIGNATURES.items())
                               + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_SPARSE_TREE_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
                               + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_POLY_SIGNATURES.items()) + list(_SQRT_SIGNATURES.items())
+                              + list(_SCAN_SIGNATURES.items())
                               + list(_ABSORB_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:

@@ -59,24 +59,7 @@ __global__ void k_vec_exp(const fe *__restrict__ a, fe e, uint64_t n, fe *__rest
 // out[]; the threads of a workgroup then share ONE Fermat inversion: prefix and suffix products of the lanes' totals (shuffles)
 // and of the waves' totals (LDS + wave 0) give every thread the inverse of its own total from the inverse of the workgroup's.
 // Pass 2 walks back.  `num` (optional) fuses the division out[i] = num[i] * a[i]^-1 (divVectorElements).
-__device__ __forceinline__ fe fe_shfl_up(const fe &v, int d) {
-    fe o;
-#pragma unroll
-    for (int l = 0; l < GF_LIMBS; l++) fe_set_limb(o, l, __shfl_up(fe_limb(v, l), d));
-    return o;
-}
-__device__ __forceinline__ fe fe_shfl_down(const fe &v, int d) {
-    fe o;
-#pragma unroll
-    for (int l = 0; l < GF_LIMBS; l++) fe_set_limb(o, l, __shfl_down(fe_limb(v, l), d));
-    return o;
-}
-__device__ __forceinline__ fe fe_shfl(const fe &v, int lane) {
-    fe o;
-#pragma unroll
-    for (int l = 0; l < GF_LIMBS; l++) fe_set_limb(o, l, __shfl(fe_limb(v, l), lane));
-    return o;
-}
+#include "fe_shfl.h"   // fe_shfl_up, fe_shfl_down, fe_shfl
 
 #ifdef GS_FIELD_128
 #include "gf128_lazy.h"

@@ -344,6 +344,276 @@ class PrimeField:
             self.backend.call('gs_field_sqrt', C.c_void_p(src.ptr), n, None, C.c_void_p(flags.ptr))
         return flags
 
+    # ---- running sums, running products and linear recurrences (include/gstark_scan.h, csrc/scan.hip)
+    MAX_SCAN_ELEMENTS = 1 << 24
+    _SCAN_OPS = {'sum': 0, 'product': 1}
+
+    def _scanEntries(self, who='PrimeField'):
+        """whether the library scans on the device; a HIP library that lacks only these entries is an error: no quiet host path"""
+        be = self.backend
+        for name in ('gs_scan', 'gs_scan_affine', 'gs_reduce', 'gs_scan_plan'):
+            if not hasattr(be.lib, name):
+                if be.name == 'hip-gfx950':
+                    raise GstarkError(f'{who}: the library has no {name} (include/gstark_scan.h)')
+                return False
+        return True
+
+    def scanPlan(self, n=0):
+        """gs_scan_plan: {'tile', 'elementsPerThread', 'maxElements', 'launches'} ('launches': what a call of n elements enqueues), or None
+        where the library has none"""
+        if not self._scanEntries():
+            return None
+        tile, per, most, launches = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint32()
+        self.backend.call('gs_scan_plan', int(n), C.byref(tile), C.byref(per), C.byref(most), C.byref(launches))
+        return {'tile': tile.value, 'elementsPerThread': per.value, 'maxElements': most.value, 'launches': launches.value}
+
+    def _scanCount(self, n, what):
+        if n > self.MAX_SCAN_ELEMENTS:
+            raise GstarkError(f'{what}: at most 2^24 elements per call, not {n}')
+        return n
+
+    def _scanValues(self, v, what):
+        try:
+            vals = [int(x) for x in v]
+        except (TypeError, ValueError):
+            raise GstarkError(f'{what}: the values are integers') from None
+        if any(not 0 <= x < self.modulus for x in vals):
+            raise GstarkError(f'{what}: a value is not a canonical element')
+        return vals
+
+    def _scanOperand(self, v, what):
+        """(Vector or None, values or None, length) of a Vector or a list of canonical elements"""
+        if isinstance(v, Vector):
+            if v.elementSize != self.elementSize:
+                raise GstarkError(f'{what}: a vector of field elements, not of {v.elementSize}-byte entries')
+            return v, None, self._scanCount(v.length, what)
+        if isinstance(v, Matrix):
+            raise GstarkError(f'{what}: a Vector or a list, not a Matrix (the MatrixRows members take one)')
+        self._scanCount(len(v) if hasattr(v, '__len__') else 0, what)
+        vals = self._scanValues(v, what)
+        return None, vals, len(vals)
+
+    def _scanMatrix(self, m, what):
+        """(Matrix or None, flat values or None, rows, cols) of a Matrix or a list of rows of equal length"""
+        if isinstance(m, Matrix):
+            if m.elementSize != self.elementSize:
+                raise GstarkError(f'{what}: a matrix of field elements, not of {m.elementSize}-byte entries')
+            rows, cols = m.rowCount, m.colCount
+            if rows and not cols:
+                raise GstarkError(f'{what}: {rows} rows of 0 columns')
+            self._scanCount(rows * cols, what)
+            return m, None, rows, cols
+        if isinstance(m, Vector):
+            raise GstarkError(f'{what}: a Matrix or a list of rows, not a Vector')
+        rows = [list(r) for r in m]
+        cols = len(rows[0]) if rows else 0
+        if any(len(r) != cols for r in rows):
+            raise GstarkError(f'{what}: the rows have different lengths')
+        if rows and not cols:
+            raise GstarkError(f'{what}: {len(rows)} rows of 0 columns')
+        self._scanCount(len(rows) * cols, what)
+        return None, self._scanValues([x for r in rows for x in r], what), len(rows), cols
+
+    def _scanHeads(self, heads, n, what):
+        """(Vector of bytes or None, list of flags or None): heads[i] & 1 starts a segment at i"""
+        if heads is None:
+            return None, None
+        if isinstance(heads, Vector):
+            if heads.elementSize != 1:
+                raise GstarkError(f'{what}: heads is a vector of bytes, not of {heads.elementSize}-byte entries')
+            if heads.length != n:
+                raise GstarkError(f'{what}: {heads.length} heads and {n} values')
+            return heads, None
+        try:
+            flags = [int(h) for h in heads]
+        except (TypeError, ValueError):
+            raise GstarkError(f'{what}: heads are bytes') from None
+        if len(flags) != n:
+            raise GstarkError(f'{what}: {len(flags)} heads and {n} values')
+        if any(not 0 <= h < 256 for h in flags):
+            raise GstarkError(f'{what}: heads are bytes')
+        return None, flags
+
+    @staticmethod
+    def _hostFlags(n, cols, heads):
+        """the head flag of every element: uniform segments of `cols`, or-ed with the low bit of the bytes"""
+        return [i % cols == 0 or bool(heads is not None and heads[i] & 1) for i in range(n)]
+
+    def _hostScan(self, op, vals, flags, exclusive):
+        p, start = self.modulus, 0 if op == 'sum' else 1
+        out, acc = [], start
+        for v, h in zip(vals, flags):
+            before = start if h else acc
+            acc = (before + v) % p if op == 'sum' else before * v % p
+            out.append(before if exclusive else acc)
+        return out
+
+    def _hostRecurrence(self, a, b, flags, x0, exclusive):
+        p, out, x = self.modulus, [], x0
+        for i, (bi, h) in enumerate(zip(b, flags)):
+            before = x0 if h else x
+            x = ((a if isinstance(a, int) else a[i]) * before + bi) % p
+            out.append(before if exclusive else x)
+        return out
+
+    @staticmethod
+    def _hostTotals(inclusive, rows, cols):
+        return [inclusive[(r + 1) * cols - 1] for r in range(rows)]
+
+    def _devicePtr(self, obj, vals):
+        """the device object of an operand given as an object or as host values"""
+        return obj if obj is not None else self.newVectorFrom(vals)
+
+    def _scanVector(self, op, v, exclusive, heads, what):
+        vec, vals, n = self._scanOperand(v, what)
+        hvec, hlist = self._scanHeads(heads, n, what)
+        if not self._scanEntries(what):
+            vals = vals if vals is not None else vec.toValues()
+            hlist = hlist if hvec is None else list(hvec.toBuffer())
+            return self.newVectorFrom(self._hostScan(op, vals, self._hostFlags(n, max(n, 1), hlist), exclusive))
+        out = Vector(self.backend, n)
+        if n:
+            src = self._devicePtr(vec, vals)
+            if hlist is not None:
+                hvec = self._flagVector(hlist)
+            self.backend.call('gs_scan', self._SCAN_OPS[op], 1 if exclusive else 0, C.c_void_p(src.ptr), C.c_void_p(hvec.ptr) if hvec is not None else None, 1, n,
+                              C.c_void_p(out.ptr), None)
+        return out
+
+    def prefixSumVectorElements(self, v, exclusive=False, heads=None):
+        """the running sums of a Vector or a list, as a Vector: out[i] = v[0] + ... + v[i], or with exclusive=True v[0] + ... + v[i-1]
+        (out[0] = 0).  heads (a Vector of bytes or a list, one per element): heads[i] & 1 starts a new segment at i, and segments
+        never influence each other.  Nothing is read back."""
+        return self._scanVector('sum', v, exclusive, heads, 'prefixSumVectorElements')
+
+    def prefixProductVectorElements(self, v, exclusive=False, heads=None):
+        """the running products: out[i] = v[0] * ... * v[i]; exclusive: out[0] = 1.  A zero zeroes the rest of its own segment only."""
+        return self._scanVector('product', v, exclusive, heads, 'prefixProductVectorElements')
+
+    def _scanRows(self, op, m, exclusive, totals, what):
+        mat, vals, rows, cols = self._scanMatrix(m, what)
+        n = rows * cols
+        if not self._scanEntries(what):
+            vals = vals if vals is not None else [x for r in mat.toValues() for x in r]
+            flags = self._hostFlags(n, max(cols, 1), None)
+            res = self._hostScan(op, vals, flags, exclusive)
+            out = self.newMatrixFrom([res[r * cols:(r + 1) * cols] for r in range(rows)]) if n else Matrix(self.backend, rows, cols)
+            if not totals:
+                return out
+            return out, self.newVectorFrom(self._hostTotals(res if not exclusive else self._hostScan(op, vals, flags, False), rows, cols))
+        out, tot = Matrix(self.backend, rows, cols), Vector(self.backend, rows) if totals else None
+        if n:
+            src = mat if mat is not None else self.newVectorFrom(vals)
+            self.backend.call('gs_scan', self._SCAN_OPS[op], 1 if exclusive else 0, C.c_void_p(src.ptr), None, rows, cols, C.c_void_p(out.ptr),
+                              C.c_void_p(tot.ptr) if totals else None)
+        return (out, tot) if totals else out
+
+    def prefixSumMatrixRows(self, m, exclusive=False, totals=False):
+        """the running sums of every row of a Matrix (or a list of rows) on its own, as a Matrix; with totals=True: (matrix, Vector of
+        the rows' sums).  One call for all the rows."""
+        return self._scanRows('sum', m, exclusive, totals, 'prefixSumMatrixRows')
+
+    def prefixProductMatrixRows(self, m, exclusive=False, totals=False):
+        """the running products of every row on its own; with totals=True: (matrix, Vector of the rows' products)"""
+        return self._scanRows('product', m, exclusive, totals, 'prefixProductMatrixRows')
+
+    def _reduceRows(self, op, src, vals, rows, cols, what):
+        """a Vector of the `rows` totals of rows * cols elements given as a device object or as values"""
+        n = rows * cols
+        if not self._scanEntries(what):
+            vals = vals if vals is not None else (src.toValues() if isinstance(src, Vector) else [x for r in src.toValues() for x in r])
+            return self.newVectorFrom(self._hostTotals(self._hostScan(op, vals, self._hostFlags(n, max(cols, 1), None), False), rows, cols) if n else [])
+        tot = Vector(self.backend, rows)
+        if n:
+            src = self._devicePtr(src, vals)
+            self.backend.call('gs_reduce', self._SCAN_OPS[op], C.c_void_p(src.ptr), rows, cols, C.c_void_p(tot.ptr))
+        return tot
+
+    def _reduceVector(self, op, v, what):
+        vec, vals, n = self._scanOperand(v, what)
+        if not n:
+            return 0 if op == 'sum' else 1
+        return self._reduceRows(op, vec, vals, 1, n, what).getValue(0)
+
+    def sumVectorElements(self, v):
+        """the sum of a Vector or a list, as an integer: one element is read back"""
+        return self._reduceVector('sum', v, 'sumVectorElements')
+
+    def prodVectorElements(self, v):
+        """the product of a Vector or a list, as an integer: one element is read back"""
+        return self._reduceVector('product', v, 'prodVectorElements')
+
+    def sumMatrixRows(self, m):
+        """a Vector of the sums of the rows of a Matrix (or a list of rows); no running values are written"""
+        mat, vals, rows, cols = self._scanMatrix(m, 'sumMatrixRows')
+        return self._reduceRows('sum', mat, vals, rows, cols, 'sumMatrixRows')
+
+    def prodMatrixRows(self, m):
+        """a Vector of the products of the rows"""
+        mat, vals, rows, cols = self._scanMatrix(m, 'prodMatrixRows')
+        return self._reduceRows('product', mat, vals, rows, cols, 'prodMatrixRows')
+
+    def _scanScalar(self, x, name, what):
+        if isinstance(x, bool) or not isinstance(x, int):
+            raise GstarkError(f'{what}: {name} is an integer')
+        if not 0 <= x < self.modulus:
+            raise GstarkError(f'{what}: {name} is not a canonical element')
+        return x
+
+    def _recurrence(self, a_obj, a_vals, a_scalar, b_obj, b_vals, rows, cols, heads, x0, exclusive, what):
+        n = rows * cols
+        hvec, hlist = heads
+        if not self._scanEntries(what):
+            flat = lambda o: o.toValues() if isinstance(o, Vector) else [x for r in o.toValues() for x in r]
+            a = a_scalar if a_scalar is not None else (a_vals if a_vals is not None else flat(a_obj))
+            b = b_vals if b_vals is not None else flat(b_obj)
+            hlist = hlist if hvec is None else list(hvec.toBuffer())
+            return self._hostRecurrence(a, b, self._hostFlags(n, max(cols, 1), hlist), x0, exclusive)
+        out = _DeviceBuffer(self.backend, n * self.elementSize)
+        if n:
+            b_src = self._devicePtr(b_obj, b_vals)
+            a_src = None if a_scalar is not None else self._devicePtr(a_obj, a_vals)
+            if hlist is not None:
+                hvec = self._flagVector(hlist)
+            self.backend.call('gs_scan_affine', 1 if exclusive else 0, C.c_void_p(a_src.ptr) if a_src is not None else None, self.le(a_scalar) if a_scalar is not None else None,
+                              C.c_void_p(b_src.ptr), self.le(x0), C.c_void_p(hvec.ptr) if hvec is not None else None, rows, cols, C.c_void_p(out.ptr))
+        return out
+
+    def linearRecurrence(self, a, b, x0=0, exclusive=False, heads=None):
+        """x[i] = a[i] * x[i-1] + b[i] with x[-1] = x0, as a Vector: out[i] = x[i], or with exclusive=True x[i-1] (out[0] = x0).  a: a Vector,
+        a list, or ONE integer for every step (a Horner chain, a geometric sum); b: a Vector or a list.  heads as in
+        prefixSumVectorElements; x0 is ONE integer that starts every segment: a start that differs from segment to segment is folded
+        into that segment's first b (b[first] + a[first] * start, x0 = 0).  Nothing is read back."""
+        what = 'linearRecurrence'
+        b_vec, b_vals, n = self._scanOperand(b, what)
+        a_vec = a_vals = a_scalar = None
+        if isinstance(a, int):
+            a_scalar = self._scanScalar(a, 'a', what)
+        else:
+            a_vec, a_vals, na = self._scanOperand(a, what)
+            if na != n:
+                raise GstarkError(f'{what}: {na} factors and {n} terms: the lengths differ')
+        x0 = self._scanScalar(x0, 'x0', what)
+        res = self._recurrence(a_vec, a_vals, a_scalar, b_vec, b_vals, 1 if n else 0, n, self._scanHeads(heads, n, what), x0, exclusive, what)
+        return self.newVectorFrom(res) if isinstance(res, list) else Vector(self.backend, n, owner=res)
+
+    def linearRecurrenceMatrixRows(self, a, b, x0=0, exclusive=False):
+        """linearRecurrence on every row of the matrices a and b (or lists of rows; a may be ONE integer) on its own, every row from x0"""
+        what = 'linearRecurrenceMatrixRows'
+        b_mat, b_vals, rows, cols = self._scanMatrix(b, what)
+        a_mat = a_vals = a_scalar = None
+        if isinstance(a, int):
+            a_scalar = self._scanScalar(a, 'a', what)
+        else:
+            a_mat, a_vals, ra, ca = self._scanMatrix(a, what)
+            if (ra, ca) != (rows, cols):
+                raise GstarkError(f'{what}: a is {ra} x {ca} and b is {rows} x {cols}: the shapes differ')
+        x0 = self._scanScalar(x0, 'x0', what)
+        res = self._recurrence(a_mat, a_vals, a_scalar, b_mat, b_vals, rows, cols, (None, None), x0, exclusive, what)
+        if isinstance(res, list):
+            return self.newMatrixFrom([res[r * cols:(r + 1) * cols] for r in range(rows)]) if rows * cols else Matrix(self.backend, rows, cols)
+        return Matrix(self.backend, rows, cols, owner=res)
+
     # ---- construction
     def newVector(self, length):
         return Vector(self.backend, length)

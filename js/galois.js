@@ -477,6 +477,134 @@ class PrimeField {
         if (v.length) this.lib.call('gs_field_sqrt', this.ctx, v.ptr, v.length, 0n, flags.ptr);
         return flags;
     }
+    // ---- running sums, running products and linear recurrences (include/gstark_scan.h, csrc/scan.hip; DESIGN 3.19).  Operands are Vectors /
+    // Matrices or arrays of BigInts, results stay on the device.  A library without the entry points (the tests' double) has no host route
+    // here: the members throw
+    _scanNeed(symbol) {
+        if (!this.lib.has || !this.lib.has(symbol)) {
+            throw new Error(`the library of the field of ${this.modulus} elements has no ${symbol} entry point (include/gstark_scan.h): scans are not computed on this device library`);
+        }
+    }
+    /** { tile, elementsPerThread, maxElements, launches } of the library's schedule (launches: what a call of n elements enqueues) */
+    scanPlan(n = 0) {
+        this._scanNeed('gs_scan_plan');
+        const tile = Buffer.alloc(4), per = Buffer.alloc(4), most = Buffer.alloc(8), launches = Buffer.alloc(4);
+        this.lib.call('gs_scan_plan', this.ctx, n, tile, per, most, launches);
+        return { tile: tile.readUInt32LE(0), elementsPerThread: per.readUInt32LE(0), maxElements: Number(most.readBigUInt64LE(0)), launches: launches.readUInt32LE(0) };
+    }
+    _scanCanonical(values, what) {
+        const vals = Array.from(values, x => BigInt(x));
+        if (vals.some(x => x < 0n || x >= this.modulus)) throw new Error(`${what}: a value is not a canonical element`);
+        return vals;
+    }
+    _scanCount(n, what) {
+        if (n > 2 ** 24) throw new Error(`${what}: at most 2^24 elements per call, not ${n}`);
+    }
+    _scanOperand(v, what) {
+        if (v instanceof Matrix) throw new Error(`${what}: a Vector or an array, not a Matrix (the MatrixRows members take one)`);
+        if (!(v instanceof Vector)) { this._scanCount(v.length, what); v = this.newVectorFrom(this._scanCanonical(v, what)); }
+        this._own(v);
+        if (v.elementSize !== this.elementSize) throw new Error(`${what}: a vector of field elements, not of ${v.elementSize}-byte entries`);
+        this._scanCount(v.length, what);
+        return v;
+    }
+    _scanMatrix(m, what) {
+        if (m instanceof Vector) throw new Error(`${what}: a Matrix or an array of rows, not a Vector`);
+        if (!(m instanceof Matrix)) {
+            const cols = m.length ? m[0].length : 0;
+            if (m.some(r => r.length !== cols)) throw new Error(`${what}: the rows have different lengths`);
+            this._scanCount(m.length * cols, what);
+            m = this.newMatrixFrom(m.map(r => this._scanCanonical(r, what)));
+        }
+        this._own(m);
+        if (m.rowCount && !m.colCount) throw new Error(`${what}: ${m.rowCount} rows of 0 columns`);
+        this._scanCount(m.rowCount * m.colCount, what);
+        return m;
+    }
+    /** heads as a Vector of bytes (heads[i] & 1 starts a segment at i), or undefined */
+    _scanHeads(heads, n, what) {
+        if (heads === undefined || heads === null) return undefined;
+        if (!(heads instanceof Vector)) {
+            const bytes = Array.from(heads, Number);
+            if (bytes.some(h => !Number.isInteger(h) || h < 0 || h > 255)) throw new Error(`${what}: heads are bytes`);
+            heads = new Vector(this, bytes.length, undefined, 0n, 1);
+            if (bytes.length) this.lib.call('gs_upload', this.ctx, heads.ptr, Buffer.from(bytes), bytes.length);
+        }
+        this._own(heads);
+        if (heads.elementSize !== 1) throw new Error(`${what}: heads is a vector of bytes, not of ${heads.elementSize}-byte entries`);
+        if (heads.length !== n) throw new Error(`${what}: ${heads.length} heads and ${n} values`);
+        return heads;
+    }
+    _scanScalar(x, name, what) {
+        if (typeof x !== 'bigint') throw new Error(`${what}: ${name} is a BigInt`);
+        if (x < 0n || x >= this.modulus) throw new Error(`${what}: ${name} is not a canonical element`);
+        return x;
+    }
+    _scanVector(op, v, exclusive, heads, what) {
+        this._scanNeed('gs_scan');
+        v = this._scanOperand(v, what);
+        heads = this._scanHeads(heads, v.length, what);
+        const out = new Vector(this, v.length);
+        if (v.length) this.lib.call('gs_scan', this.ctx, op, exclusive ? 1 : 0, v.ptr, heads ? heads.ptr : 0n, 1, v.length, out.ptr, 0n);
+        return out;
+    }
+    /** out[i] = v[0] + ... + v[i] (exclusive: ... + v[i-1], out[0] = 0); heads: bytes whose low bit starts a new segment.  Nothing read back */
+    prefixSumVectorElements(v, exclusive = false, heads) { return this._scanVector(0, v, exclusive, heads, 'prefixSumVectorElements'); }
+    /** out[i] = v[0] * ... * v[i] (exclusive: out[0] = 1); a zero zeroes the rest of its own segment only */
+    prefixProductVectorElements(v, exclusive = false, heads) { return this._scanVector(1, v, exclusive, heads, 'prefixProductVectorElements'); }
+    _scanRows(op, m, exclusive, totals, what) {
+        this._scanNeed('gs_scan');
+        m = this._scanMatrix(m, what);
+        const out = new Matrix(this, m.rowCount, m.colCount), tot = totals ? new Vector(this, m.rowCount) : undefined;
+        if (m.rowCount * m.colCount) this.lib.call('gs_scan', this.ctx, op, exclusive ? 1 : 0, m.ptr, 0n, m.rowCount, m.colCount, out.ptr, tot ? tot.ptr : 0n);
+        return totals ? { matrix: out, totals: tot } : out;
+    }
+    /** the running sums of every row on its own, as a Matrix; totals = true: { matrix, totals: Vector of the rows' sums } */
+    prefixSumMatrixRows(m, exclusive = false, totals = false) { return this._scanRows(0, m, exclusive, totals, 'prefixSumMatrixRows'); }
+    prefixProductMatrixRows(m, exclusive = false, totals = false) { return this._scanRows(1, m, exclusive, totals, 'prefixProductMatrixRows'); }
+    _reduceRows(op, src, rows, cols) {
+        this._scanNeed('gs_reduce');
+        const tot = new Vector(this, rows);
+        if (rows * cols) this.lib.call('gs_reduce', this.ctx, op, src.ptr, rows, cols, tot.ptr);
+        return tot;
+    }
+    /** the sum / the product of a Vector or an array, as a BigInt: one element is read back */
+    sumVectorElements(v) { this._scanNeed('gs_reduce'); v = this._scanOperand(v, 'sumVectorElements'); return v.length ? this._reduceRows(0, v, 1, v.length).getValue(0) : 0n; }
+    prodVectorElements(v) { this._scanNeed('gs_reduce'); v = this._scanOperand(v, 'prodVectorElements'); return v.length ? this._reduceRows(1, v, 1, v.length).getValue(0) : 1n; }
+    /** a Vector of the sums / the products of the rows; no running values are written */
+    sumMatrixRows(m) { this._scanNeed('gs_reduce'); m = this._scanMatrix(m, 'sumMatrixRows'); return this._reduceRows(0, m, m.rowCount, m.colCount); }
+    prodMatrixRows(m) { this._scanNeed('gs_reduce'); m = this._scanMatrix(m, 'prodMatrixRows'); return this._reduceRows(1, m, m.rowCount, m.colCount); }
+    /** x[i] = a[i] * x[i-1] + b[i], x[-1] = x0: out[i] = x[i] (exclusive: x[i-1], out[0] = x0).  a: a Vector, an array, or ONE BigInt for every
+     *  step; x0 starts every segment (a start per segment is folded into that segment's first b) */
+    linearRecurrence(a, b, x0 = 0n, exclusive = false, heads) {
+        const what = 'linearRecurrence';
+        this._scanNeed('gs_scan_affine');
+        b = this._scanOperand(b, what);
+        const scalar = typeof a === 'bigint' ? this._scanScalar(a, 'a', what) : undefined;
+        if (scalar === undefined) {
+            a = this._scanOperand(a, what);
+            if (a.length !== b.length) throw new Error(`${what}: ${a.length} factors and ${b.length} terms: the lengths differ`);
+        }
+        x0 = this._scanScalar(x0, 'x0', what);
+        heads = this._scanHeads(heads, b.length, what);
+        const out = new Vector(this, b.length);
+        if (b.length) this.lib.call('gs_scan_affine', this.ctx, exclusive ? 1 : 0, scalar === undefined ? a.ptr : 0n, this.le(scalar === undefined ? 0n : scalar), b.ptr, this.le(x0), heads ? heads.ptr : 0n, 1, b.length, out.ptr);
+        return out;
+    }
+    linearRecurrenceMatrixRows(a, b, x0 = 0n, exclusive = false) {
+        const what = 'linearRecurrenceMatrixRows';
+        this._scanNeed('gs_scan_affine');
+        b = this._scanMatrix(b, what);
+        const scalar = typeof a === 'bigint' ? this._scanScalar(a, 'a', what) : undefined;
+        if (scalar === undefined) {
+            a = this._scanMatrix(a, what);
+            if (a.rowCount !== b.rowCount || a.colCount !== b.colCount) throw new Error(`${what}: a is ${a.rowCount} x ${a.colCount} and b is ${b.rowCount} x ${b.colCount}: the shapes differ`);
+        }
+        x0 = this._scanScalar(x0, 'x0', what);
+        const out = new Matrix(this, b.rowCount, b.colCount);
+        if (b.rowCount * b.colCount) this.lib.call('gs_scan_affine', this.ctx, exclusive ? 1 : 0, scalar === undefined ? a.ptr : 0n, this.le(scalar === undefined ? 0n : scalar), b.ptr, this.le(x0), 0n, b.rowCount, b.colCount, out.ptr);
+        return out;
+    }
     // ---- long polynomials at arbitrary points (include/gstark_poly.h, csrc/poly.hip; DESIGN 3.16).  Operands are Vectors or arrays of
     // BigInts, results stay on the device.  A library without the entry points (the tests' double) has no host route here: the members throw
     _polyNeed(symbol) {

@@ -161,6 +161,12 @@ const FnDesc kFns[] = {
     {"gs_curve_lift_x", "cbbppupp"},
     {"gs_curve_compress", "cpupp"},
     {"gs_field_sqrt_plan", "coooo"},
+    // include/gstark_scan.h: OPTIONAL in the same way; `heads`, `totals_out` and the affine entry's `a` may be 0 (a = 0: the factor is the
+    // host element that follows it); the plan's results are host uint32, uint32, uint64, uint32
+    {"gs_scan", "ciippuupp"},
+    {"gs_scan_affine", "cipbpbpuup"},
+    {"gs_reduce", "cipuup"},
+    {"gs_scan_plan", "cuoooo"},
     // include/gstark_absorb.h: OPTIONAL in the same way; the handles are those of gs_hades_create / gs_rescue_create
     {"gs_hades_absorb", "cppuiuuiip"},
     {"gs_rescue_absorb", "cppuiuuiiip"},
