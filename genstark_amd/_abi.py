@@ -262,6 +262,13 @@ _DIAGNOSE_SIGNATURES = {
 }
 DIAGNOSE_SYMBOLS = tuple(_DIAGNOSE_SIGNATURES)
 
+# include/gstark_debug.h: a test hook on the context's block cache; optional in the same way (Backend.cache_fill says so where a library
+# lacks it; nothing in production calls it)
+_DEBUG_SIGNATURES = {
+    'gs_cache_fill': (_int, [_vp, C.c_uint8, C.POINTER(_u64), C.POINTER(_u64)]),
+}
+DEBUG_SYMBOLS = tuple(_DEBUG_SIGNATURES)
+
 
 class GstarkError(RuntimeError):
     pass
@@ -280,7 +287,7 @@ def load_library(path):
                               + list(_TREE_UPDATE_SIGNATURES.items()) + list(_TREE_VERIFY_SIGNATURES.items()) + list(_SPARSE_TREE_SIGNATURES.items()) + list(_MIMC_SIGNATURES.items())
                               + list(_CURVE_SIGNATURES.items()) + list(_MSM_SIGNATURES.items()) + list(_POLY_SIGNATURES.items()) + list(_SQRT_SIGNATURES.items())
                               + list(_SCAN_SIGNATURES.items())
-                              + list(_ABSORB_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items())):
+                              + list(_ABSORB_SIGNATURES.items()) + list(_DIAGNOSE_SIGNATURES.items()) + list(_DEBUG_SIGNATURES.items())):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args
@@ -382,6 +389,17 @@ class Backend:
     def trim(self):
         """Give the cached device blocks back to the driver (long-running services with changing problem sizes)."""
         self.call('gs_cache_trim')
+
+    def cache_fill(self, byte):
+        """Fill every cached (freed) device block with `byte`, behind everything enqueued so far: gs_cache_fill (include/gstark_debug.h),
+        a test hook.  Returns (blocks, bytes) filled."""
+        if not hasattr(self.lib, 'gs_cache_fill'):
+            raise GstarkError(f'the {self.name} library has no gs_cache_fill (include/gstark_debug.h): its block cache cannot be filled')
+        if not 0 <= int(byte) <= 255:
+            raise GstarkError(f'cache_fill: {byte} is not a byte')
+        blocks, nbytes = C.c_uint64(), C.c_uint64()
+        self.call('gs_cache_fill', int(byte), C.byref(blocks), C.byref(nbytes))
+        return blocks.value, nbytes.value
 
     def upload(self, ptr, data):
         self.call('gs_upload', C.c_void_p(ptr), bytes(data), len(data))

@@ -409,6 +409,7 @@ int gs_air_constraints_strided(gs_ctx *c, const uint32_t *code_host, uint32_t ni
         if (jrc == GS_OK) { gs_tmp_free(c, dprog); return GS_OK; }
     }
     dim3 grid(gs_grid(nc)), block(256);
+    gs_traffic(c, nc * ((uint64_t)registers + constraints) * GS_ELT, nc * constraints, "k_air_constraints");      // (as gs_jit_constraints tallies the compiled form)
     if (vm_regs <= 16)
         hipLaunchKernelGGL(k_air_constraints<16>, grid, block, 0, c->stream, dcode, ninstr, dconst, (const fe *)p_comp, nc, shift % nc, (const fe *)static_tables, prog.sd, (fe *)out, prow, pstride);
     else if (vm_regs <= 32)
@@ -460,6 +461,7 @@ int gs_air_trace_segments(gs_ctx *c, const uint32_t *code_host, uint32_t ninstr,
     }
     dim3 block(64), grid((unsigned)((segments * lanes + 63) / 64));   // one wave per 64 / lanes segments: the few long-running threads spread over the CUs
     const uint64_t lds_bytes = ((uint64_t)vm_regs + 2ull * registers) * 64 * GS_ELT;
+    gs_traffic(c, (uint64_t)registers * segments * (segment_len + 1) * GS_ELT, (uint64_t)registers * segments * segment_len, "k_air_trace_segments");      // (as gs_jit_trace)
 #define GS_LAUNCH_TRACE(N, L, SH)                                                                                                        \
     hipLaunchKernelGGL((k_air_trace_segments<N, L>), grid, block, SH, c->stream, dcode, ninstr, dinit, init_ninstr, dconst, dstat, prog.sd, drows, \
                        registers, segments, segment_len, vm_regs, lanes, (fe *)out)

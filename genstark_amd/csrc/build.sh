@@ -5,7 +5,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=1000000 -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result"
 UNITS="ctx ntt pointwise hash air_mimc air_vm air_jit small boundary hades rescue field_tree curve msm poly sqrt scan diagnose"
-HDRS="gf128_lazy.h host_pow.h air_program.h air_codegen.h jit_build.h gf128.h gf_small.h gf_wide.h common.h sponge_common.h field_tree.h tree_update_plan.h sparse_tree_plan.h tree_verify.h curve_jac.h msm_plan.h poly_plan.h sqrt_plan.h scan_plan.h fe_shfl.h host_field.h host_field_small.h host_field_wide.h host_poly.h host_hash.h hash_core.h ../../include/gstark.h ../../include/gstark_boundary.h ../../include/gstark_mimc.h ../../include/gstark_hades.h ../../include/gstark_rescue.h ../../include/gstark_tree_update.h ../../include/gstark_tree_verify.h ../../include/gstark_sparse_tree.h ../../include/gstark_curve.h ../../include/gstark_msm.h ../../include/gstark_poly.h ../../include/gstark_sqrt.h ../../include/gstark_scan.h ../../include/gstark_absorb.h ../../include/gstark_diagnose.h ../../include/gstark_prover.h"
+HDRS="gf128_lazy.h host_pow.h air_program.h air_codegen.h jit_build.h gf128.h gf_small.h gf_wide.h common.h sponge_common.h field_tree.h tree_update_plan.h sparse_tree_plan.h tree_verify.h curve_jac.h msm_plan.h poly_plan.h sqrt_plan.h scan_plan.h fe_shfl.h host_field.h host_field_small.h host_field_wide.h host_poly.h host_hash.h hash_core.h ../../include/gstark.h ../../include/gstark_boundary.h ../../include/gstark_mimc.h ../../include/gstark_hades.h ../../include/gstark_rescue.h ../../include/gstark_tree_update.h ../../include/gstark_tree_verify.h ../../include/gstark_sparse_tree.h ../../include/gstark_curve.h ../../include/gstark_msm.h ../../include/gstark_poly.h ../../include/gstark_sqrt.h ../../include/gstark_scan.h ../../include/gstark_absorb.h ../../include/gstark_diagnose.h ../../include/gstark_debug.h ../../include/gstark_prover.h"
 # one library per field: the 128-bit field of the hot path, and two "plumbing" flavours of the same sources for the small prime
 # fields of the reference's examples (gf_small.h): 2^64 - 21*2^30 + 1 (rescue/hash2x64.ts) and 2^32 - 3*2^25 + 1 (demo/fibonacci.ts)
 # the field headers as string literals: the source text hiprtc compiles AIR programs against (air_jit.hip)

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "../../include/gstark_debug.h"
 #include <chrono>
 #include <sched.h>
 #include <time.h>
@@ -201,6 +202,22 @@ int gs_cache_trim(gs_ctx *c) {
     for (auto &kv : c->free_blocks) hipFree(kv.second);
     c->free_blocks.clear();
     c->cached_bytes = 0;
+    return GS_OK;
+}
+
+// include/gstark_debug.h: every cached block holds `byte` throughout, as if the harshest previous user had left it (a test hook)
+int gs_cache_fill(gs_ctx *c, uint8_t byte, uint64_t *blocks, uint64_t *bytes) {
+    if (!c) return GS_ERR_ARG;
+    uint64_t nb = 0, total = 0;
+    std::lock_guard<std::mutex> lock(c->blocks_mutex);
+    GS_HIP(c, hipSetDevice(c->device));
+    for (auto &kv : c->free_blocks) {
+        GS_HIP(c, hipMemsetAsync(kv.second, byte, kv.first, c->stream));
+        nb++;
+        total += kv.first;
+    }
+    if (blocks) *blocks = nb;
+    if (bytes) *bytes = total;
     return GS_OK;
 }
 

@@ -580,6 +580,8 @@ int gs_hash_merge_rows(gs_ctx *c, gs_hash_alg alg, const void *const *vecs_host,
         void *tab = nullptr;
         if ((rc = gs_tmp_alloc(c, (uint64_t)count * sizeof(void *), &tab))) return rc;
         if ((rc = gs_push(c, tab, vecs_host, (uint64_t)count * sizeof(void *)))) { gs_tmp_free(c, tab); return rc; }      // vecs_host belongs to the caller
+        gs_traffic(c, n * ((uint64_t)count * GS_ELT + 32), n * hash_blocks(alg == GS_HASH_SHA256 ? 0 : 1, (uint64_t)count * GS_ELT), "k_hash_merge_rows_table<%d>",
+                   alg == GS_HASH_SHA256 ? 0 : 1);
         if (alg == GS_HASH_SHA256)
             hipLaunchKernelGGL(k_hash_merge_rows_table<0>, dim3(gs_grid(n)), dim3(256), 0, c->stream, (const uint4 *const *)tab, count, n, (uint4 *)out);
         else

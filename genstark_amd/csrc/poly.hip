@@ -351,6 +351,7 @@ int divide(const Run &r, const poly_div_plan &d, const fe *a, const fe *b, fe *q
     if (r_out && d.lr) {
         fe *qb = r.at(d.off_qb);
         if ((rc = product_range(r, d.back, q, b, 0, d.lr, qb))) return rc;
+        gs_traffic(r.c, 3 * d.lr * GS_ELT, 0, "k_poly_remainder");
         POLY_LAUNCH(r, k_poly_remainder, d.lr, a, qb, d.lr, r_out);
     }
     return GS_OK;
